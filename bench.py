@@ -9,6 +9,7 @@ A "step" is one pass of the hot path over one resident batch: ONE launch of the 
     python bench.py --gpus N --config 3      # N = 1, 2, 4, 8: the sweep at configs[3]'s per-GPU shape (131 072 x 1 KB each;
                                              # at N = 8 that is BASELINE configs[3] itself, 1 Mi streams)
     python bench.py --gpus 8 --config 4      # configs[4] stand-in: snort_16 on 4 KB T windows, 131 072 per GPU
+    python bench.py --dump-outputs DIR       # also writes the last timed step's outputs as DIR/*.npy (to compare builds)
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8   # what the driver does: same result
 
 With N>1 every rank (one process per GPU) owns its own contiguous block of streams of the same generator —
@@ -72,7 +73,12 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) for real multi-GPU runs; gloo only to rehearse ranks on fewer GPUs")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: every rank uses GPU 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's block) as DIR/<name>.npy "
+                         "(float64, at most 64 MiB in all; a fixed seeded sample of the streams)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = a.config if a.config is not None else 2
     ns, sl, wl, desc = CONFIGS[cfg]
     a.config = cfg
@@ -118,6 +124,40 @@ def make_rows(rx, workload, first, count, stream_len, traces):
     if workload == "R":
         return wl.ruleset_traffic(traces, count, stream_len, first=first)
     return wl.uniform(count, stream_len, first=first)
+
+
+DUMP_LIMIT = 64 << 20  # bytes of .npy payload that --dump-outputs may write
+DUMP_SEED = 20261015
+
+
+def dump_outputs(path, res, first, nw64):
+    """What plan.download() handed back after the last timed step, as float64 .npy files (every value is an integer
+    below 2^53, so exact): the accept totals per state over the whole batch, and for a fixed seeded sample of the streams
+    their any-match bitmap words, final active sets as 32-bit words (low half of each 64-bit word first) and accept
+    events (stream, k, state).  Stream ids are global (rank block offset `first` added)."""
+    import numpy as np
+    totals = res["match_count_total"].astype(np.float64)
+    am, fin = res["anymatch"], res["final_active"]
+    ns = am.shape[0]
+    per_stream = 8 * (am.shape[1] + 2 * nw64)
+    rows_budget = (DUMP_LIMIT - totals.nbytes) // 2
+    k = max(1, min(ns, rows_budget // per_stream))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(ns, size=k, replace=False))
+    ev = res["events"]
+    ev = ev[np.isin(ev["stream"], pick)]
+    ev = ev[:(DUMP_LIMIT - totals.nbytes - k * (per_stream + 8)) // 24]  # (events are in (stream, k, state) order)
+    arrays = {
+        "match_count_total": totals,
+        "stream_ids": (pick + first).astype(np.float64),
+        "anymatch": am[pick].astype(np.float64),
+        "final_active": np.ascontiguousarray(fin[pick]).view("<u4").astype(np.float64),
+        "events": np.stack([ev["stream"].astype(np.float64) + first, ev["k"].astype(np.float64),
+                            ev["state"].astype(np.float64)], axis=1).reshape(-1, 3),
+    }
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_LIMIT
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def time_kernel(plan, steps):
@@ -227,6 +267,8 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res, first, nfa.nw64)
 
     gbit = 8.0 * bytes_total * a.steps / sec / 1e9
     npass = sl + 1

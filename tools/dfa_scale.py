@@ -1,6 +1,6 @@
 import importlib, os, sys
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 rx = importlib.import_module("regex-fpga_amd"); wl = rx.workloads
 import torch
 snort = rx.Nfa.load_coe(wl.SNORT_COE)
