@@ -8,6 +8,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstddef>
@@ -19,6 +20,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "rx_internal.hpp"
@@ -63,7 +65,64 @@ extern "C" const char* rx_strerror(int code) {
 extern "C" const char* rx_last_hip_error(void) { return g_last_hip.c_str(); }
 extern "C" int rx_abi_version(void) { return RX_ABI_VERSION; }
 
+// ---- owned HIP objects ------------------------------------------------------------------------------
+// `n` elements of device memory or (Pinned) page-locked host memory, freed by the owner's destructor.  The current device
+// must be the one the memory lives on whenever it is allocated or freed.
+template <typename T, bool Pinned = false>
+struct HipBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  HipBuf() = default;
+  HipBuf(HipBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  HipBuf(const HipBuf&) = delete;
+  HipBuf& operator=(const HipBuf&) = delete;
+  ~HipBuf() { release(); }
+  void release() {
+    if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    n = 0;
+  }
+  // room for at least `need` elements; when it has to grow, the old contents are dropped and `alloc` (>= need) are taken
+  int grow(size_t need, size_t alloc = 0) {
+    if (need <= n) return RX_OK;
+    release();
+    const size_t bytes = std::max(need, alloc) * sizeof(T);
+    const hipError_t e = Pinned ? hipHostMalloc((void**)&p, bytes, hipHostMallocDefault) : hipMalloc((void**)&p, bytes);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return hip_fail(e, Pinned ? "hipHostMalloc" : "hipMalloc");
+    }
+    n = std::max(need, alloc);
+    return RX_OK;
+  }
+};
+
+struct HipEvent {
+  hipEvent_t e = nullptr;
+  HipEvent() = default;
+  HipEvent(HipEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
+  HipEvent(const HipEvent&) = delete;
+  HipEvent& operator=(const HipEvent&) = delete;
+  ~HipEvent() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  int create(unsigned flags = hipEventDefault) {
+    HIPCHK(hipEventCreateWithFlags(&e, flags));
+    return RX_OK;
+  }
+};
+
+// the caller's current device, restored when the scope ends
+struct DeviceScope {
+  int prev = -1;
+  bool have = hipGetDevice(&prev) == hipSuccess;
+  ~DeviceScope() {
+    if (have) (void)hipSetDevice(prev);
+  }
+};
+
 // ---- automaton ------------------------------------------------------------------------------------
+// A plain view of the automaton's tables on one device: plans copy it by value; DevCopy owns the buffers.
 struct DevTables {
   uint32_t* words = nullptr;
   uint32_t* symidx = nullptr;
@@ -79,12 +138,28 @@ struct DevTables {
   uint32_t dfa_pool_chunks = 0, dfa_hash_mask = 0;
   int cu_count = 0;
   size_t lds_per_cu = 0;
+  std::array<uint32_t*, 14> bufs() const {
+    return {words, symidx, ovf, accept_bits, symidx_c, symidx_p, ovf_dir, pin_tab, regidx, byte_class,
+            dfa_trans, dfa_pool, dfa_hash, dfa_hdr};
+  }
+};
+
+// The owner of one device's tables (freed with that device current)
+struct DevCopy {
+  DevTables t;
+  DevCopy() = default;
+  DevCopy(DevCopy&& o) noexcept : t(o.t) { o.t = DevTables{}; }
+  DevCopy(const DevCopy&) = delete;
+  DevCopy& operator=(const DevCopy&) = delete;
+  ~DevCopy() {
+    for (uint32_t* b : t.bufs()) (void)hipFree(b);
+  }
 };
 
 struct rx_nfa {
   RxHostNfa h;
   std::mutex mu;
-  std::map<int, DevTables> dev;  // HBM copies, one per device, uploaded on first use
+  std::map<int, DevCopy> dev;  // HBM copies, one per device, uploaded on first use
   std::vector<int32_t> accept_pattern;  // filled by rx_compile_patterns
   // AUTO, batches too small for a probe: do few of the cells the register kernel would place from hold lists?  (-1: not
   // looked at yet; the index is immutable, so the answer is computed once, under mu)
@@ -168,26 +243,8 @@ extern "C" const uint32_t* rx_nfa_words(const rx_nfa* nfa, size_t* nwords) {
 
 extern "C" void rx_nfa_free(rx_nfa* nfa) {
   if (!nfa) return;
-  int prev = -1;
-  bool have_prev = hipGetDevice(&prev) == hipSuccess;
-  for (auto& kv : nfa->dev) {
-    if (hipSetDevice(kv.first) != hipSuccess) continue;
-    (void)hipFree(kv.second.words);
-    (void)hipFree(kv.second.symidx);
-    (void)hipFree(kv.second.ovf);
-    (void)hipFree(kv.second.accept_bits);
-    (void)hipFree(kv.second.symidx_c);
-    (void)hipFree(kv.second.symidx_p);
-    (void)hipFree(kv.second.ovf_dir);
-    (void)hipFree(kv.second.pin_tab);
-    (void)hipFree(kv.second.regidx);
-    (void)hipFree(kv.second.byte_class);
-    (void)hipFree(kv.second.dfa_trans);
-    (void)hipFree(kv.second.dfa_pool);
-    (void)hipFree(kv.second.dfa_hash);
-    (void)hipFree(kv.second.dfa_hdr);
-  }
-  if (have_prev) (void)hipSetDevice(prev);
+  DeviceScope keep;
+  for (auto it = nfa->dev.begin(); it != nfa->dev.end(); it = nfa->dev.erase(it)) (void)hipSetDevice(it->first);
   delete nfa;
 }
 
@@ -241,8 +298,9 @@ static int get_dev_tables(const rx_nfa* cnfa, int device, DevTables* out) {
   rx_nfa* nfa = const_cast<rx_nfa*>(cnfa);
   std::lock_guard<std::mutex> lk(nfa->mu);
   auto it = nfa->dev.find(device);
-  if (it != nfa->dev.end()) { *out = it->second; return RX_OK; }
-  DevTables t;
+  if (it != nfa->dev.end()) { *out = it->second.t; return RX_OK; }
+  DevCopy c;  // (what was uploaded before a failing upload is freed with it)
+  DevTables& t = c.t;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
   t.cu_count = prop.multiProcessorCount;
@@ -263,8 +321,8 @@ static int get_dev_tables(const rx_nfa* cnfa, int device, DevTables* out) {
     memcpy(bc.data(), nfa->h.byte_class, 256);
     if ((rc = upload_vec(bc, &t.byte_class))) return rc;
   }
-  nfa->dev[device] = t;
   *out = t;
+  nfa->dev.emplace(device, std::move(c));
   return RX_OK;
 }
 
@@ -290,7 +348,7 @@ static int dfa_init_tables(const rx_nfa* nfa, DevTables& t) {
 static int ensure_dfa_tables(const rx_nfa* cnfa, int device, DevTables* out) {
   rx_nfa* nfa = const_cast<rx_nfa*>(cnfa);
   std::lock_guard<std::mutex> lk(nfa->mu);
-  DevTables& t = nfa->dev[device];
+  DevTables& t = nfa->dev[device].t;
   if (!t.dfa_trans) {
     t.dfa_pool_chunks = 1u << 18;  // 262 144 chunks of 128 B: up to that many DFA states (32 MB)
     t.dfa_hash_mask = (1u << 19) - 1;
@@ -313,13 +371,11 @@ extern "C" int rx_nfa_dfa_info(const rx_nfa* cnfa, int device, uint64_t* n_state
   if (n_states) *n_states = 0;
   if (n_transitions) *n_transitions = 0;
   auto it = nfa->dev.find(device);
-  if (it == nfa->dev.end() || !it->second.dfa_hdr) return RX_OK;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
+  if (it == nfa->dev.end() || !it->second.t.dfa_hdr) return RX_OK;
+  DeviceScope keep;
   HIPCHK(hipSetDevice(device));
   uint32_t hdr[4] = {0, 0, 0, 0};
-  HIPCHK(hipMemcpy(hdr, it->second.dfa_hdr, sizeof(hdr), hipMemcpyDeviceToHost));
-  if (prev >= 0) (void)hipSetDevice(prev);
+  HIPCHK(hipMemcpy(hdr, it->second.t.dfa_hdr, sizeof(hdr), hipMemcpyDeviceToHost));
   if (n_states) *n_states = hdr[2];
   if (n_transitions) *n_transitions = hdr[3];
   return RX_OK;
@@ -332,14 +388,11 @@ extern "C" int rx_nfa_dfa_reset(const rx_nfa* cnfa, int device) {
   rx_nfa* nfa = const_cast<rx_nfa*>(cnfa);
   std::lock_guard<std::mutex> lk(nfa->mu);
   auto it = nfa->dev.find(device);
-  if (it == nfa->dev.end() || !it->second.dfa_trans) return RX_OK;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
+  if (it == nfa->dev.end() || !it->second.t.dfa_trans) return RX_OK;
+  DeviceScope keep;
   HIPCHK(hipSetDevice(device));
   HIPCHK(hipDeviceSynchronize());
-  int rc = dfa_init_tables(nfa, it->second);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  return rc;
+  return dfa_init_tables(nfa, it->second.t);
   RX_CATCH
 }
 
@@ -353,78 +406,77 @@ struct rx_plan {
   size_t max_streams = 0, max_len = 0, events_cap = 0;
   bool want_mc = false, want_am = false, want_final = false;
   // device buffers
-  uint8_t* d_in_own = nullptr;
-  size_t d_in_own_bytes = 0;
+  HipBuf<uint8_t> d_in_own;
   const uint8_t* d_in = nullptr;
-  rx_event* d_events = nullptr;
+  HipBuf<rx_event> d_events;
   // two sets of {counters[16], match_count_total[size]} that alternate between launches: the kernel zeroes the set of
   // the NEXT launch (RxParams::zero_next), so no reset has to be enqueued between two launches
-  unsigned long long* d_cset[2] = {nullptr, nullptr};
+  HipBuf<unsigned long long> d_cset[2];
   int cur_set = 0;             // the set the LAST launch used (what download reads)
   bool sets_clean = false;     // both sets are zero except for what the last launch accumulated in d_cset[cur_set]
   unsigned long long* d_counters = nullptr;  // == d_cset[cur_set]
-  uint32_t* d_mc = nullptr;
+  HipBuf<uint32_t> d_mc;
   unsigned long long* d_mct = nullptr;
-  uint32_t* d_am = nullptr;
-  uint32_t* d_final = nullptr;
+  HipBuf<uint32_t> d_am;
+  HipBuf<uint32_t> d_final;
   // rx_plan_run, compact final sets (on request): states per block of streams, offset / count per stream
-  uint32_t* d_fstates = nullptr;
+  HipBuf<uint32_t> d_fstates, d_foff, d_fcnt;
   // rx_plan_run: page-locked staging for the two downloads whose sizes are only known once the counters are on the host
   // (accept events, compact final lists); grown on demand
-  void* h_stage_ev = nullptr;
-  size_t h_stage_ev_bytes = 0;
-  void* h_stage_fs = nullptr;
-  size_t h_stage_fs_bytes = 0;
-  uint32_t *d_foff = nullptr, *d_fcnt = nullptr;
-  size_t fstates_cap = 0;
-  uint32_t* d_init = nullptr;
+  HipBuf<rx_event, true> h_stage_ev;
+  HipBuf<uint32_t, true> h_stage_fs;
+  HipBuf<uint32_t> d_init;  // start sets, rows of 2 * nw64 words
   bool have_init = false;             // start sets belong to ONE batch: every new input clears the flag
   std::vector<uint64_t> init_stage;   // host staging of the caller's start sets (tail bits masked)
-  uint32_t *d_spill_streams = nullptr, *d_spill_k = nullptr, *d_spill_rows = nullptr;
+  HipBuf<uint32_t> d_spill_streams, d_spill_k, d_spill_rows;
   size_t am_stride = 0;
   // current batch
   size_t n_streams = 0, stream_len = 0, stride = 0;
   bool have_input = false, launched = false;
-  bool auto_decided = false;   // RX_KERNEL_AUTO: the probe's decision is valid for the current batch
+  bool auto_decided = false;   // RX_KERNEL_AUTO: `choice` is valid for the current batch
   uint32_t batches_since_probe = 0;
-  // AUTO's decisions by batch shape (ceil log2 of the stream count and of the stream length): a plan that is fed
-  // alternating shapes probes each of them once, not on every change.  `pinned`: made by rx_plan_tune — never probed again.
+  // AUTO's decision.  `pinned`: made by rx_plan_tune — never probed again.
   struct AutoChoice {
-    uint32_t kernel = RX_KERNEL_SYM_PACK, lanes = 16;
-    bool prune = false, fold = false, reg_skip = true, probe_prune = false, pinned = false;
-    double probe_active = 0;
+    uint32_t kernel = RX_KERNEL_SYM_PACK;
+    uint32_t lanes = 16;    // streams per wavefront chosen for the pack kernel
+    bool prune = false;     // look-ahead pruning chosen (and verified at `lanes`) by the probe
+    bool fold = false;      // always-on-state folding chosen (and verified at `lanes`) by the probe
+    bool reg_skip = true;   // register kernel: the build that steps over idle passes (AUTO's trial / timed choice)
+    bool probe_prune = false;  // the probe's statistics say pruning pays (used when the caller fixes the kernel)
+    bool pinned = false;
+    double probe_active = 0;   // active states per stream-byte seen by the probe
   };
+  AutoChoice choice;  // the current decision
+  // AUTO's decisions by batch shape (ceil log2 of the stream count and of the stream length): a plan that is fed
+  // alternating shapes probes each of them once, not on every change
   std::map<uint32_t, AutoChoice> choices;
   uint32_t shape_key = 0;
-  bool choice_pinned = false;  // the current decision came from rx_plan_tune
   bool tuning = false;         // inside rx_plan_tune: probe even under RX_OPT_NO_PROBE
-  uint32_t auto_kernel = RX_KERNEL_SYM_PACK;
-  uint32_t auto_lanes = 16;    // streams per wavefront chosen for the pack kernel
-  bool auto_prune = false;     // look-ahead pruning chosen (and verified at auto_lanes) by the probe
-  bool auto_fold = false;      // always-on-state folding chosen (and verified at auto_lanes) by the probe
-  bool auto_reg_skip = true;   // register kernel: the build that steps over idle passes (AUTO's trial / timed choice)
-  bool probe_prune = false;    // the probe's statistics say pruning pays (used when the caller fixes the kernel)
-  double probe_active = 0;     // active states per stream-byte seen by the probe
   RxParams params{};
   RxLaunchCfg cfg{};
   // rx_plan_run: blocks of streams in flight on their own HIP streams
   struct Pipe {
-    unsigned long long* d_set = nullptr;   // {counters[16], match_count_total[size]} of the block (device)
-    unsigned long long* h_set = nullptr;   // the same, page-locked host memory
-    hipEvent_t up = nullptr;               // the block's input is in HBM
-    hipEvent_t k0 = nullptr, k1 = nullptr; // bracket the block's kernels
+    HipBuf<unsigned long long> d_set;        // {counters[16], match_count_total[size]} of the block (device)
+    HipBuf<unsigned long long, true> h_set;  // the same, page-locked host memory
+    HipEvent up;                             // the block's input is in HBM
+    HipEvent k0, k1;                         // bracket the block's kernels
   };
   std::vector<Pipe> pipes;
   hipStream_t s_in = nullptr, s_k = nullptr, s_out = nullptr;  // uploads / kernels / downloads of rx_plan_run
   // rx_plan_run: one capacity for the whole call.  d_run_ctr[0] = accept events of all blocks so far (their slot counter),
   // [1] = entries of the compact final sets so far, [2 + b] / [10 + b] = those two after block b (snapshots taken on the
   // kernel stream, so that the host can cut the shared buffers back into blocks); h_run_ctr: page-locked copy
-  unsigned long long* d_run_ctr = nullptr;
-  unsigned long long* h_run_ctr = nullptr;
+  HipBuf<unsigned long long> d_run_ctr;
+  HipBuf<unsigned long long, true> h_run_ctr;
   // one hipEvent pair per launch since the last rx_plan_kernel_times() call
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+  std::vector<std::pair<HipEvent, HipEvent>> evs;
   size_t n_timed = 0;
   double last_ms = 0;
+  // (the plan's device must be current: rx_plan_free)
+  ~rx_plan() {
+    for (hipStream_t s : {s_in, s_k, s_out})
+      if (s) (void)hipStreamDestroy(s);
+  }
 };
 
 // struct_size == 0 was documented by ABI 1 as "this version": its meaning is frozen at the ABI-1 layouts (rx_opts up to
@@ -476,7 +528,7 @@ extern "C" int rx_plan_create(const rx_nfa* nfa, const rx_opts* opts, size_t max
     if (e != hipSuccess) return hip_fail(e, "hipGetDeviceCount");
     if (ndev <= 0) return RX_ENODEVICE;
   }
-  rx_plan* p = new (std::nothrow) rx_plan();
+  std::unique_ptr<rx_plan> p(new (std::nothrow) rx_plan());  // (freed on every error path, with its device current)
   if (!p) return RX_ENOMEM;
   p->nfa = nfa;
   p->opts = o;
@@ -488,68 +540,34 @@ extern "C" int rx_plan_create(const rx_nfa* nfa, const rx_opts* opts, size_t max
   p->want_am = want_anymatch != 0;
   p->want_final = want_final != 0;
   int rc = bind_device(o.device, &p->device);
-  if (rc) { delete p; return rc; }
+  if (rc) return rc;
   rc = get_dev_tables(nfa, p->device, &p->tab);
-  if (rc) { delete p; return rc; }
+  if (rc) return rc;
   const uint32_t size = nfa->h.size;
-  const size_t nw64x2 = 2 * (((size_t)size + 63) / 64);
-  auto fail = [&](int code) { rx_plan_free(p); return code; };
-#define PLCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(hip_fail(e_, #call)); } while (0)
-  for (int q = 0; q < 2; q++) {
-    PLCHK(hipMalloc((void**)&p->d_cset[q], (16 + (size_t)size) * sizeof(unsigned long long)));
-    PLCHK(hipMemset(p->d_cset[q], 0, (16 + (size_t)size) * sizeof(unsigned long long)));
+  const size_t nw64x2 = 2 * (((size_t)size + 63) / 64), set_words = 16 + (size_t)size;
+  for (auto& set : p->d_cset) {
+    if ((rc = set.grow(set_words))) return rc;
+    HIPCHK(hipMemset(set.p, 0, set_words * sizeof(unsigned long long)));
   }
-  p->d_counters = p->d_cset[0];
-  p->d_mct = p->d_cset[0] + 16;
+  p->d_counters = p->d_cset[0].p;
+  p->d_mct = p->d_counters + 16;
   p->sets_clean = true;
-  PLCHK(hipMalloc((void**)&p->d_events, std::max<size_t>(events_cap, 1) * sizeof(rx_event)));
-  if (p->want_mc) PLCHK(hipMalloc((void**)&p->d_mc, max_streams * size * sizeof(uint32_t)));
+  if ((rc = p->d_events.grow(std::max<size_t>(events_cap, 1)))) return rc;
+  if (p->want_mc && (rc = p->d_mc.grow(max_streams * size))) return rc;
   // rows of the plan's any-match bitmap: padded to a multiple of eight words, so that the pack kernel's 256-pass groups are
   // aligned 32-byte sectors (a caller whose anymatch_stride is the same gets flat copies, any other stride row-by-row ones)
   p->am_stride = ((size_t)((passes_for(max_stream_len, RX_MODE_FULL) + 31) / 32) + 7) & ~(size_t)7;
-  if (p->want_am) PLCHK(hipMalloc((void**)&p->d_am, max_streams * p->am_stride * sizeof(uint32_t)));
-  if (p->want_final) PLCHK(hipMalloc((void**)&p->d_final, max_streams * nw64x2 * sizeof(uint32_t)));
-#undef PLCHK
-  *out = p;
+  if (p->want_am && (rc = p->d_am.grow(max_streams * p->am_stride))) return rc;
+  if (p->want_final && (rc = p->d_final.grow(max_streams * nw64x2))) return rc;
+  *out = p.release();
   return RX_OK;
   RX_CATCH
 }
 
 extern "C" void rx_plan_free(rx_plan* p) {
   if (!p) return;
-  int prev = -1;
-  bool have_prev = hipGetDevice(&prev) == hipSuccess;
+  DeviceScope keep;
   (void)hipSetDevice(p->device);
-  (void)hipFree(p->d_in_own);
-  (void)hipFree(p->d_events);
-  (void)hipFree(p->d_cset[0]);
-  (void)hipFree(p->d_cset[1]);
-  (void)hipFree(p->d_mc);
-  (void)hipFree(p->d_am);
-  (void)hipFree(p->d_final);
-  (void)hipFree(p->d_fstates);
-  if (p->h_stage_ev) (void)hipHostFree(p->h_stage_ev);
-  if (p->h_stage_fs) (void)hipHostFree(p->h_stage_fs);
-  (void)hipFree(p->d_foff);
-  (void)hipFree(p->d_fcnt);
-  (void)hipFree(p->d_init);
-  (void)hipFree(p->d_spill_streams);
-  (void)hipFree(p->d_spill_k);
-  (void)hipFree(p->d_spill_rows);
-  (void)hipFree(p->d_run_ctr);
-  if (p->h_run_ctr) (void)hipHostFree(p->h_run_ctr);
-  for (auto& e : p->evs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  for (auto& q : p->pipes) {
-    (void)hipFree(q.d_set);
-    if (q.h_set) (void)hipHostFree(q.h_set);
-    if (q.up) (void)hipEventDestroy(q.up);
-    if (q.k0) (void)hipEventDestroy(q.k0);
-    if (q.k1) (void)hipEventDestroy(q.k1);
-  }
-  if (p->s_in) (void)hipStreamDestroy(p->s_in);
-  if (p->s_k) (void)hipStreamDestroy(p->s_k);
-  if (p->s_out) (void)hipStreamDestroy(p->s_out);
-  if (have_prev) (void)hipSetDevice(prev);
   delete p;
 }
 
@@ -557,20 +575,6 @@ static uint32_t ceil_log2(size_t v) {
   uint32_t b = 0;
   while (b < 63 && ((size_t)1 << b) < v) b++;
   return b;
-}
-
-static void store_choice(rx_plan* p, bool pinned) {
-  rx_plan::AutoChoice c;
-  c.kernel = p->auto_kernel;
-  c.lanes = p->auto_lanes;
-  c.prune = p->auto_prune;
-  c.fold = p->auto_fold;
-  c.reg_skip = p->auto_reg_skip;
-  c.probe_prune = p->probe_prune;
-  c.probe_active = p->probe_active;
-  c.pinned = pinned;
-  p->choices[p->shape_key] = c;
-  p->choice_pinned = pinned;
 }
 
 static int set_batch(rx_plan* p, size_t n_streams, size_t stream_len, size_t stride) {
@@ -585,21 +589,13 @@ static int set_batch(rx_plan* p, size_t n_streams, size_t stream_len, size_t str
     auto it = p->choices.find(p->shape_key);
     p->batches_since_probe = 0;
     if (it != p->choices.end()) {
-      const rx_plan::AutoChoice& c = it->second;
-      p->auto_kernel = c.kernel;
-      p->auto_lanes = c.lanes;
-      p->auto_prune = c.prune;
-      p->auto_fold = c.fold;
-      p->auto_reg_skip = c.reg_skip;
-      p->probe_prune = c.probe_prune;
-      p->probe_active = c.probe_active;
-      p->choice_pinned = c.pinned;
+      p->choice = it->second;
       p->auto_decided = true;
     } else {
       p->auto_decided = false;
-      p->choice_pinned = false;
+      p->choice.pinned = false;
     }
-  } else if (!p->choice_pinned && !(p->opts.flags & RX_OPT_NO_PROBE) && ++p->batches_since_probe >= 32) {
+  } else if (!p->choice.pinned && !(p->opts.flags & RX_OPT_NO_PROBE) && ++p->batches_since_probe >= 32) {
     p->auto_decided = false;
     p->batches_since_probe = 0;
   }
@@ -612,6 +608,23 @@ static int set_batch(rx_plan* p, size_t n_streams, size_t stream_len, size_t str
   return RX_OK;
 }
 
+// Rows [s0, s0 + n) of the batch set_batch took, from the caller's array (rows `stride` apart) into the plan's input
+// buffer, on `s`.  The buffer holds the whole batch at a 4-byte-aligned pitch, so that every lane can take a whole dword.
+static int upload_rows(rx_plan* p, const uint8_t* bytes, size_t stride, size_t s0, size_t n, hipStream_t s) {
+  const size_t len = p->stream_len, pitch = (len + 3) & ~(size_t)3;
+  const int rc = p->d_in_own.grow(std::max<size_t>(p->n_streams * pitch, 4));
+  if (rc) return rc;
+  p->d_in = p->d_in_own.p;
+  p->stride = pitch;
+  if (!len) return RX_OK;
+  uint8_t* dst = p->d_in_own.p + s0 * pitch;
+  if (stride == pitch && len == pitch)  // rows packed without padding: one flat copy (the 2-D path is slower from pageable memory)
+    HIPCHK(hipMemcpyAsync(dst, bytes + s0 * stride, n * pitch, hipMemcpyHostToDevice, s));
+  else
+    HIPCHK(hipMemcpy2DAsync(dst, pitch, bytes + s0 * stride, stride, len, n, hipMemcpyHostToDevice, s));
+  return RX_OK;
+}
+
 extern "C" int rx_plan_upload(rx_plan* p, const uint8_t* bytes, size_t n_streams, size_t stream_len,
                               size_t stride) {
   RX_TRY
@@ -621,26 +634,7 @@ extern "C" int rx_plan_upload(rx_plan* p, const uint8_t* bytes, size_t n_streams
   if (rc) return rc;
   rc = set_batch(p, n_streams, stream_len, stride);
   if (rc) return rc;
-  // rows are packed to a 4-byte-aligned pitch in HBM so every lane can take a whole dword
-  const size_t pitch = (stream_len + 3) & ~(size_t)3;
-  const size_t need = std::max<size_t>(n_streams * pitch, 4);
-  if (need > p->d_in_own_bytes) {
-    (void)hipFree(p->d_in_own);
-    p->d_in_own = nullptr;
-    p->d_in_own_bytes = 0;
-    HIPCHK(hipMalloc((void**)&p->d_in_own, need));
-    p->d_in_own_bytes = need;
-  }
-  if (stream_len) {
-    if (stride == pitch && stream_len == pitch)  // rows packed without padding: one flat copy (the 2-D path is slower from pageable memory)
-      HIPCHK(hipMemcpyAsync(p->d_in_own, bytes, n_streams * pitch, hipMemcpyHostToDevice, p->stream));
-    else
-      HIPCHK(hipMemcpy2DAsync(p->d_in_own, pitch, bytes, stride, stream_len, n_streams, hipMemcpyHostToDevice,
-                              p->stream));
-  }
-  p->d_in = p->d_in_own;
-  p->stride = pitch;
-  return RX_OK;
+  return upload_rows(p, bytes, stride, 0, n_streams, p->stream);
   RX_CATCH
 }
 
@@ -665,9 +659,9 @@ extern "C" int rx_plan_set_init_active(rx_plan* p, const uint64_t* init_active) 
   if (rc) return rc;
   const uint32_t size = p->nfa->h.size;
   const size_t nw64 = ((size_t)size + 63) / 64;
-  if (!p->d_init) {
-    HIPCHK(hipMalloc((void**)&p->d_init, p->max_streams * nw64 * sizeof(uint64_t)));
-    HIPCHK(hipMemsetAsync(p->d_init, 0, p->max_streams * nw64 * sizeof(uint64_t), p->stream));
+  if (!p->d_init.p) {
+    if ((rc = p->d_init.grow(p->max_streams * nw64 * 2))) return rc;
+    HIPCHK(hipMemsetAsync(p->d_init.p, 0, p->max_streams * nw64 * sizeof(uint64_t), p->stream));
   }
   // Bits at or above `size` in a row's last word name states that do not exist (the kernels would index the
   // tables with them): they are cleared in a staging copy, which also makes the call safe to return from — the
@@ -681,7 +675,7 @@ extern "C" int rx_plan_set_init_active(rx_plan* p, const uint64_t* init_active) 
     const uint64_t keep = (1ull << (size & 63u)) - 1ull;
     for (size_t s = 0; s < p->n_streams; s++) p->init_stage[s * nw64 + nw64 - 1] &= keep;
   }
-  HIPCHK(hipMemcpyAsync(p->d_init, p->init_stage.data(), p->n_streams * nw64 * sizeof(uint64_t), hipMemcpyHostToDevice,
+  HIPCHK(hipMemcpyAsync(p->d_init.p, p->init_stage.data(), p->n_streams * nw64 * sizeof(uint64_t), hipMemcpyHostToDevice,
                         p->stream));
   HIPCHK(hipStreamSynchronize(p->stream));  // pageable staging memory: the copy has left it when this returns
   p->have_init = true;
@@ -718,15 +712,45 @@ static void fill_common(rx_plan* p, RxParams& a) {
 }
 
 static int ensure_spill_area(rx_plan* p, RxParams& a) {
-  if (!p->d_spill_rows) {  // hand-off area group/pack kernel -> wave kernel, sized so that it cannot overflow
-    HIPCHK(hipMalloc((void**)&p->d_spill_streams, p->max_streams * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void**)&p->d_spill_k, p->max_streams * sizeof(uint32_t)));
-    HIPCHK(hipMalloc((void**)&p->d_spill_rows, p->max_streams * (size_t)a.nw64x2 * sizeof(uint32_t)));
-  }
+  // hand-off area group/pack kernel -> wave kernel, sized so that it cannot overflow
+  int rc;
+  if ((rc = p->d_spill_streams.grow(p->max_streams)) || (rc = p->d_spill_k.grow(p->max_streams)) ||
+      (rc = p->d_spill_rows.grow(p->max_streams * (size_t)a.nw64x2)))
+    return rc;
   a.spill_count = p->d_counters + 3;
-  a.spill_streams = p->d_spill_streams;
-  a.spill_k = p->d_spill_k;
-  a.spill_rows = p->d_spill_rows;
+  a.spill_streams = p->d_spill_streams.p;
+  a.spill_k = p->d_spill_k.p;
+  a.spill_rows = p->d_spill_rows.p;
+  return RX_OK;
+}
+
+// One run of AUTO's probes over the first `len` bytes of the first `n_streams` streams of the batch (`n_passes` accept
+// checks each), no outputs.  `want` names the kernel and the few build choices that differ between the probes (lanes,
+// stats, prune, fold, reg_skip).  The counters are zeroed first; then either they are read back into cnt[16] (the stream is
+// synchronised), or the launch is bracketed by the event pair ev[2].  The probe accumulates into the current set of
+// counters: both sets are reset before the real launch.
+static int sample_launch(rx_plan* p, RxLaunchCfg want, size_t n_streams, size_t len, uint32_t n_passes,
+                         unsigned long long* cnt, const HipEvent* ev = nullptr) {
+  RxParams a;
+  fill_common(p, a);
+  a.n_streams = (uint32_t)n_streams;
+  a.stream_len = (uint32_t)len;
+  a.n_passes = n_passes;
+  a.n_consume = a.stream_len;
+  RxLaunchCfg cfg = want;
+  int rc = rx_pick_launch(want.kernel, a.size, a.n_streams, p->tab.cu_count, p->tab.lds_per_cu, &a, &cfg);
+  if (rc) return rc;
+  if ((rc = ensure_spill_area(p, a))) return rc;
+  p->sets_clean = false;
+  HIPCHK(hipMemsetAsync(p->d_counters, 0, 16 * sizeof(unsigned long long), p->stream));
+  if (ev) HIPCHK(hipEventRecord(ev[0].e, p->stream));
+  const hipError_t e = (hipError_t)rx_launch(a, cfg, p->stream);
+  if (e != hipSuccess) return hip_fail(e, "probe launch");
+  if (ev) HIPCHK(hipEventRecord(ev[1].e, p->stream));
+  if (cnt) {
+    HIPCHK(hipMemcpyAsync(cnt, p->d_counters, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+  }
   return RX_OK;
 }
 
@@ -734,12 +758,13 @@ static int ensure_spill_area(rx_plan* p, RxParams& a) {
 // the input.  Probe: the pack kernel's statistics build over a corner of the batch (512 K stream-bytes: the first <= 4096
 // bytes of <= 512 streams, no outputs), then: small active sets -> pack kernel, larger ones -> wavefront-per-stream slice kernel.
 static int auto_probe_pack(rx_plan* p) {
-  p->auto_kernel = RX_KERNEL_SYM_PACK;
-  p->auto_lanes = 16;
-  p->auto_prune = false;
-  p->auto_fold = false;
-  p->probe_prune = false;
-  p->probe_active = 0;
+  rx_plan::AutoChoice& ch = p->choice;  // (reg_skip is left as it is)
+  ch.kernel = RX_KERNEL_SYM_PACK;
+  ch.lanes = 16;
+  ch.prune = false;
+  ch.fold = false;
+  ch.probe_prune = false;
+  ch.probe_active = 0;
   if (p->n_streams * p->stream_len < (256u << 10)) return RX_OK;  // tiny batch: not worth a probe
   // one run of the pack kernel with `lanes` streams per wavefront over the corner of the batch: the statistics
   // build (counters) or, with stats = false, the build that would really run (only the hand-off count is read)
@@ -748,34 +773,21 @@ static int auto_probe_pack(rx_plan* p) {
   const size_t sample_len = std::min<size_t>(p->stream_len, 4096);
   const size_t sample_streams = std::min<size_t>(p->n_streams, std::max<size_t>(128, (512u << 10) / std::max<size_t>(sample_len, 1)));
   unsigned long long cnt[16];
-  bool run_fold = false;  // the next run() uses the FOLD build
-  auto run = [&](uint32_t lanes, bool stats, bool prune, double* spilled) -> int {
-    RxParams a;
-    fill_common(p, a);
-    a.n_streams = (uint32_t)sample_streams;
-    a.stream_len = (uint32_t)sample_len;
-    a.n_passes = a.stream_len + 1;
-    a.n_consume = a.stream_len;
-    RxLaunchCfg cfg{};
-    cfg.group_lanes = lanes;
-    int rc = rx_pick_launch(RX_KERNEL_SYM_PACK, a.size, a.n_streams, p->tab.cu_count, p->tab.lds_per_cu, &a, &cfg);
+  auto run = [&](uint32_t lanes, bool stats, bool prune, bool fold, double* spilled) -> int {
+    RxLaunchCfg want{};
+    want.kernel = RX_KERNEL_SYM_PACK;
+    want.group_lanes = lanes;
+    want.stats = stats;
+    want.prune = prune;
+    want.fold = fold;
+    const int rc = sample_launch(p, want, sample_streams, sample_len, (uint32_t)sample_len + 1, cnt);
     if (rc) return rc;
-    cfg.stats = stats;
-    cfg.prune = prune;
-    cfg.fold = run_fold && !stats;
-    if ((rc = ensure_spill_area(p, a))) return rc;
-    HIPCHK(hipMemsetAsync(p->d_counters, 0, 16 * sizeof(unsigned long long), p->stream));
-    p->sets_clean = false;  // (the probe accumulates into the current set; both are reset before the real launch)
-    hipError_t e = (hipError_t)rx_launch(a, cfg, p->stream);
-    if (e != hipSuccess) return hip_fail(e, "probe launch");
-    HIPCHK(hipMemcpyAsync(cnt, p->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    *spilled = (double)cnt[3] / a.n_streams;
+    *spilled = (double)cnt[3] / (double)sample_streams;
     return RX_OK;
   };
   const double units = (double)sample_streams * (double)std::max<size_t>(sample_len, 1);
   double spilled = 0;
-  int rc = run(16, true, false, &spilled);
+  int rc = run(16, true, false, false, &spilled);
   if (rc) return rc;
   // (When only a few streams left the sample run, the pack kernel's own share of the active states is the better measure of
   // how full its lists are: what a stream that was handed off does afterwards, on the wave kernel, says nothing about them —
@@ -783,7 +795,7 @@ static int auto_probe_pack(rx_plan* p) {
   // BEFORE they left and says nothing either: then the total stands.)
   const double spilled16 = spilled;
   const double active = (double)((spilled16 <= 0.05 && cnt[7]) ? cnt[7] : cnt[1]) / units;
-  p->probe_active = active;
+  ch.probe_active = active;
   // the pack kernel is fastest when one pass of a wavefront is ONE sweep with 30-37 of the 64 lanes busy:
   // streams per wavefront ~ 33 / (list entries per stream)   (snort_16: T 2.3 -> 13, U 1.15 -> 32)
   // A batch that cannot give every SIMD at least two wavefronts at that size is latency-bound (a wavefront alone on
@@ -813,7 +825,7 @@ static int auto_probe_pack(rx_plan* p) {
             active, 100.0 * spilled16, 100.0 * (double)cnt[5] / own, 100.0 * (double)cnt[6] / own);
   // (pruning must remove at least a tenth of the entries to pay for its directory look-ups: l7-filter meets
   // multi-target rows in every pass but nearly all of their targets live on)
-  p->probe_prune = p->tab.ovf_dir && (double)cnt[5] / own >= 0.02 && (double)cnt[6] / own >= 0.10;
+  ch.probe_prune = p->tab.ovf_dir && (double)cnt[5] / own >= 0.02 && (double)cnt[6] / own >= 0.10;
   // (With the narrow pruned index the PRUNE build also drops INLINE targets that die on the next byte — -21 % list entries
   // on the snort_16 trace windows.  Measured this round it does not pay on its own: the PRUNE pass reads a second class
   // byte and carries the look-ahead layout, and costs more than the entries it saves at every batch size — 65 536
@@ -829,11 +841,8 @@ static int auto_probe_pack(rx_plan* p) {
   // reads how many entries were left, and takes it below 0.3 per stream-byte.  Streams per wavefront: as many as still
   // give every SIMD two wavefronts (16 ... 64).
   if (p->tab.pin_tab && !(p->opts.flags & RX_OPT_NO_FOLD) && active <= 3.0) {
-    const bool prune = p->probe_prune && !(p->opts.flags & RX_OPT_NO_PRUNE);
-    run_fold = true;
-    rc = run(32, false, prune, &spilled);
-    run_fold = false;
-    if (rc) return rc;
+    const bool prune = ch.probe_prune && !(p->opts.flags & RX_OPT_NO_PRUNE);
+    if ((rc = run(32, false, prune, true, &spilled))) return rc;
     const double left = (double)cnt[7] / units;
     static const uint32_t fold_s[] = {16, 24, 32, 48, 64};
     uint32_t lanes = 16;
@@ -845,27 +854,27 @@ static int auto_probe_pack(rx_plan* p) {
     if (left <= 0.03) lanes = per_simd >= 48.0 ? 16u : 8u;
     if (dbg) fprintf(stderr, "[rxmatch] probe: folded build leaves %.3f list entries per stream-byte, hand-offs %.1f %% -> %s\n", left,
                      100.0 * spilled, (left <= 0.3 && spilled <= 0.02) ? "fold" : "no fold");
-    if (left <= 0.3 && spilled <= 0.02) { p->auto_lanes = lanes; p->auto_fold = true; p->auto_prune = prune; return RX_OK; }
+    if (left <= 0.3 && spilled <= 0.02) { ch.lanes = lanes; ch.fold = true; ch.prune = prune; return RX_OK; }
   }
-  if (p->probe_prune && !(p->opts.flags & RX_OPT_NO_PRUNE)) {
+  if (ch.probe_prune && !(p->opts.flags & RX_OPT_NO_PRUNE)) {
     const double entries = std::min(active * (1.0 - dead_frac), left_pruned);
     if (entries <= 6.0) {
       const uint32_t lanes = lanes_for(entries);
-      if ((rc = run(lanes, false, true, &spilled))) return rc;
-      if (spilled <= 0.02) { p->auto_lanes = lanes; p->auto_prune = true; return RX_OK; }
+      if ((rc = run(lanes, false, true, false, &spilled))) return rc;
+      if (spilled <= 0.02) { ch.lanes = lanes; ch.prune = true; return RX_OK; }
     }
-    if ((rc = run(4, false, true, &spilled))) return rc;
-    if (spilled <= 0.02) { p->auto_lanes = 4; p->auto_prune = true; return RX_OK; }
+    if ((rc = run(4, false, true, false, &spilled))) return rc;
+    if (spilled <= 0.02) { ch.lanes = 4; ch.prune = true; return RX_OK; }
   }
   if (active <= 6.0 && spilled16 <= 0.02) {
-    p->auto_lanes = lanes_for(active);
+    ch.lanes = lanes_for(active);
     return RX_OK;
   }
   // many active states per stream: four streams per wavefront with the long list (512 entries) and the wider
   // filters, if that form keeps (nearly) all of the sample; otherwise one wavefront per stream
-  if ((rc = run(4, true, false, &spilled))) return rc;
-  if (spilled <= 0.02) p->auto_lanes = 4;
-  else p->auto_kernel = RX_KERNEL_SYM_WAVE;
+  if ((rc = run(4, true, false, false, &spilled))) return rc;
+  if (spilled <= 0.02) ch.lanes = 4;
+  else ch.kernel = RX_KERNEL_SYM_WAVE;
   return RX_OK;
 }
 
@@ -881,6 +890,7 @@ static int auto_probe(rx_plan* p, bool reg_eligible) {
   int rc = auto_probe_pack(p);
   if (rc || !reg_eligible) return rc;
   const RxHostNfa& h = p->nfa->h;
+  rx_plan::AutoChoice& ch = p->choice;
   if (p->n_streams * p->stream_len < (256u << 10)) {
     rx_nfa* n = const_cast<rx_nfa*>(p->nfa);
     {
@@ -891,49 +901,29 @@ static int auto_probe(rx_plan* p, bool reg_eligible) {
         n->few_lists = ov * 4u <= nz ? 1 : 0;
       }
     }
-    if (n->few_lists == 1) p->auto_kernel = RX_KERNEL_SYM_REG;
-    p->auto_reg_skip = !h.pin_tab.empty();
+    if (n->few_lists == 1) ch.kernel = RX_KERNEL_SYM_REG;
+    ch.reg_skip = !h.pin_tab.empty();
     return RX_OK;
   }
-  if (p->auto_kernel != RX_KERNEL_SYM_PACK) return RX_OK;  // (many active states per stream: neither of the two)
-  struct EventPair {  // (destroyed on every path out of the probe)
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } ev;
-  HIPCHK(hipEventCreate(&ev.a));
-  HIPCHK(hipEventCreate(&ev.b));
-  const hipEvent_t e0 = ev.a, e1 = ev.b;
+  if (ch.kernel != RX_KERNEL_SYM_PACK) return RX_OK;  // (many active states per stream: neither of the two)
+  HipEvent ev[2];
+  if ((rc = ev[0].create()) || (rc = ev[1].create())) return rc;
   // one warm-up launch on the probe's corner of the batch (the first launch of a kernel pays for its code object), then
   // the WHOLE batch, timed, without outputs: between 4 and 16 wavefronts per SIMD neither kernel's time can be read off
   // a smaller sample (the register kernel grows with the batch, the pack kernel does not), and the batch is small
   auto timed = [&](uint32_t kernel, bool reg_skip, float* ms) -> int {
-    for (int it = 0; it < 2; it++) {
-      RxParams a;
-      fill_common(p, a);
-      a.n_streams = it == 0 ? (uint32_t)std::min<size_t>(p->n_streams, 512) : (uint32_t)p->n_streams;
-      a.stream_len = it == 0 ? (uint32_t)std::min<size_t>(p->stream_len, 1024) : (uint32_t)p->stream_len;
-      a.n_passes = a.stream_len + 1;
-      a.n_consume = a.stream_len;
-      RxLaunchCfg cfg{};
-      cfg.group_lanes = p->auto_lanes;
-      int r = rx_pick_launch(kernel, a.size, a.n_streams, p->tab.cu_count, p->tab.lds_per_cu, &a, &cfg);
-      if (r) return r;
-      cfg.prune = kernel == RX_KERNEL_SYM_PACK && p->auto_prune;
-      cfg.fold = kernel == RX_KERNEL_SYM_REG ? p->tab.pin_tab != nullptr : p->auto_fold;
-      cfg.reg_skip = reg_skip;
-      if ((r = ensure_spill_area(p, a))) return r;
-      p->sets_clean = false;
-      HIPCHK(hipMemsetAsync(p->d_counters, 0, 16 * sizeof(unsigned long long), p->stream));
-      HIPCHK(hipEventRecord(e0, p->stream));
-      hipError_t e = (hipError_t)rx_launch(a, cfg, p->stream);
-      if (e != hipSuccess) return hip_fail(e, "probe launch");
-      HIPCHK(hipEventRecord(e1, p->stream));
-    }
+    RxLaunchCfg want{};
+    want.kernel = kernel;
+    want.group_lanes = ch.lanes;
+    want.prune = kernel == RX_KERNEL_SYM_PACK && ch.prune;
+    want.fold = kernel == RX_KERNEL_SYM_REG ? p->tab.pin_tab != nullptr : ch.fold;
+    want.reg_skip = reg_skip;
+    const size_t warm_len = std::min<size_t>(p->stream_len, 1024);
+    int r = sample_launch(p, want, std::min<size_t>(p->n_streams, 512), warm_len, (uint32_t)warm_len + 1, nullptr, ev);
+    if (!r) r = sample_launch(p, want, p->n_streams, p->stream_len, (uint32_t)p->stream_len + 1, nullptr, ev);
+    if (r) return r;
     HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipEventElapsedTime(ms, e0, e1));
+    HIPCHK(hipEventElapsedTime(ms, ev[0].e, ev[1].e));
     return RX_OK;
   };
   float t_pack = 0.f, t_reg = 0.f, t_skip = 0.f;
@@ -944,16 +934,13 @@ static int auto_probe(rx_plan* p, bool reg_eligible) {
   if (p->opts.flags & RX_OPT_VERBOSE)
     fprintf(stderr, "[rxmatch] probe: the batch on the pack kernel %.3f ms, one wavefront per stream %.3f ms, stepping over idle "
                     "passes %.3f ms\n", t_pack, t_reg, t_skip);
-  p->auto_reg_skip = t_skip < t_reg;
-  if (std::min(t_reg, t_skip) < 0.95f * t_pack) p->auto_kernel = RX_KERNEL_SYM_REG;
+  ch.reg_skip = t_skip < t_reg;
+  if (std::min(t_reg, t_skip) < 0.95f * t_pack) ch.kernel = RX_KERNEL_SYM_REG;
   return RX_OK;
 }
 
-// Everything a launch decides before anything is enqueued for it: kernel arguments for the whole batch (p->params),
-// kernel choice (AUTO's probe runs here when its decision is not valid for the batch) and launch geometry (p->cfg).
-static int prepare_launch(rx_plan* p) {
-  int rc;
-  const RxHostNfa& h = p->nfa->h;
+// The kernel arguments for the whole batch (p->params), up to the launch geometry and the hand-off area
+static int batch_params(rx_plan* p) {
   RxParams& a = p->params;
   fill_common(p, a);
   a.n_streams = (uint32_t)p->n_streams;
@@ -962,130 +949,147 @@ static int prepare_launch(rx_plan* p) {
   a.n_consume = p->opts.mode == RX_MODE_TB_COMPAT ? a.n_passes : (uint32_t)p->stream_len;
   if (p->opts.k_base + a.n_passes > (1ull << 32)) return RX_EINVAL;  // rx_event.k would wrap
   a.k_base = (uint32_t)p->opts.k_base;
-  a.init_active = p->have_init ? p->d_init : nullptr;
-  a.events = p->events_cap ? p->d_events : nullptr;
+  a.init_active = p->have_init ? p->d_init.p : nullptr;
+  a.events = p->events_cap ? p->d_events.p : nullptr;
   a.events_cap = (uint32_t)p->events_cap;
-  a.match_count = p->want_mc ? p->d_mc : nullptr;
+  a.match_count = p->want_mc ? p->d_mc.p : nullptr;
   a.match_count_total = p->d_mct;
-  a.anymatch = p->want_am ? p->d_am : nullptr;
+  a.anymatch = p->want_am ? p->d_am.p : nullptr;
   a.anymatch_stride = (uint32_t)p->am_stride;
-  a.final_active = p->want_final ? p->d_final : nullptr;
-  uint32_t kernel = p->opts.kernel;
-  uint32_t auto_lanes = 0;
+  a.final_active = p->want_final ? p->d_final.p : nullptr;
+  // the testbench's clock count needs both streams of a pair in one wavefront: pack kernel only
   const bool pair = p->opts.collect_stats == 2;
-  if (pair) {  // the testbench's clock count needs both streams of a pair in one wavefront: pack kernel only
-    if ((kernel != RX_KERNEL_AUTO && kernel != RX_KERNEL_SYM_PACK) || (p->n_streams & 1) || p->have_init) return RX_EINVAL;
-    kernel = RX_KERNEL_SYM_PACK;
-  }
+  if (pair && ((p->opts.kernel != RX_KERNEL_AUTO && p->opts.kernel != RX_KERNEL_SYM_PACK) || (p->n_streams & 1) || p->have_init))
+    return RX_EINVAL;
   a.pair_cycles = pair ? 1u : 0u;
+  return RX_OK;
+}
+
+// The kernel for the batch, before the rules of resolve_cfg.  AUTO, and an explicit RX_KERNEL_SYM_PACK (whether look-ahead
+// pruning pays depends on the input), make p->choice valid for the batch: the shape's decision, or a new one from the probes.
+static int decide_kernel(rx_plan* p, uint32_t* out) {
+  const rx_opts& o = p->opts;
+  rx_plan::AutoChoice& ch = p->choice;
+  const bool pair = o.collect_stats == 2;
+  uint32_t kernel = pair ? RX_KERNEL_SYM_PACK : o.kernel;
   // few long streams from reset (the reference's own run is one lock-step pair): latency per pass is what counts, and the
   // register-resident kernel has the shortest pass; it has no statistics build
-  const bool reg_ok = p->opts.collect_stats == 0 && !p->have_init && p->tab.regidx;
+  const bool reg_ok = o.collect_stats == 0 && !p->have_init && p->tab.regidx;
   // RX_OPT_NO_PROBE: nothing below may run a kernel or wait for the stream; a shape rx_plan_tune has not seen gets the
   // defaults (the pack kernel at 16 streams per wavefront; up to 4 streams the register kernel's skipping build)
-  const bool may_probe = p->tuning || !(p->opts.flags & RX_OPT_NO_PROBE);
+  const bool may_probe = p->tuning || !(o.flags & RX_OPT_NO_PROBE);
+  int rc;
   if (kernel == RX_KERNEL_AUTO && p->n_streams <= 4 && reg_ok) {
     kernel = RX_KERNEL_SYM_REG;
-    if (!p->auto_decided && !may_probe) {
-      p->auto_reg_skip = true;
-      p->auto_decided = true;
-    }
     if (!p->auto_decided) {
       // Which build: a trial run over the first 8 192 bytes with the one that steps over idle passes, which counts the
       // groups of passes it skipped in the second half (the busier shipped trace: none after pass 680 — the `.*` states
       // inside its patterns never leave once entered; the quieter one: 63 %).
-      p->auto_reg_skip = true;
-      if (p->stream_len >= 16384) {
-        RxParams t;
-        fill_common(p, t);
-        t.n_streams = (uint32_t)p->n_streams;
-        t.stream_len = 8192u;
-        t.n_passes = t.n_consume = 8192u;
-        RxLaunchCfg cfg{};
-        if ((rc = rx_pick_launch(RX_KERNEL_SYM_REG, t.size, t.n_streams, p->tab.cu_count, p->tab.lds_per_cu, &t, &cfg))) return rc;
-        cfg.fold = p->tab.pin_tab != nullptr;
-        cfg.reg_skip = true;
-        if ((rc = ensure_spill_area(p, t))) return rc;
-        p->sets_clean = false;
+      ch.reg_skip = true;
+      if (may_probe && p->stream_len >= 16384) {
+        RxLaunchCfg want{};
+        want.kernel = RX_KERNEL_SYM_REG;
+        want.fold = p->tab.pin_tab != nullptr;
+        want.reg_skip = true;
         unsigned long long cnt[16];
-        HIPCHK(hipMemsetAsync(p->d_counters, 0, sizeof(cnt), p->stream));
-        hipError_t e = (hipError_t)rx_launch(t, cfg, p->stream);
-        if (e != hipSuccess) return hip_fail(e, "trial launch");
-        HIPCHK(hipMemcpyAsync(cnt, p->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(hipStreamSynchronize(p->stream));
-        p->auto_reg_skip = cnt[10] * 10u >= (unsigned long long)t.n_streams * 1024u;  // >= 10 % of the 1 024 groups per stream
-        if (p->opts.flags & RX_OPT_VERBOSE)
-          fprintf(stderr, "[rxmatch] register kernel trial: %llu of %u groups of passes idle -> %s\n", cnt[10], t.n_streams * 1024u,
-                  p->auto_reg_skip ? "step over them" : "plain build");
+        if ((rc = sample_launch(p, want, p->n_streams, 8192, 8192, cnt))) return rc;
+        const uint32_t groups = (uint32_t)p->n_streams * 1024u;
+        ch.reg_skip = cnt[10] * 10u >= (unsigned long long)groups;  // >= 10 % of the 1 024 groups per stream
+        if (o.flags & RX_OPT_VERBOSE)
+          fprintf(stderr, "[rxmatch] register kernel trial: %llu of %u groups of passes idle -> %s\n", cnt[10], groups,
+                  ch.reg_skip ? "step over them" : "plain build");
+      }
+      if (may_probe) {
+        ch.pinned = p->tuning;
+        p->choices[p->shape_key] = ch;
       }
       p->auto_decided = true;
-      store_choice(p, p->tuning);
     }
-  }
-  // (more streams, but at most 16 wavefronts of them per SIMD: the probe times both kernels on the batch)
-  const bool reg_eligible = kernel == RX_KERNEL_AUTO && reg_ok && p->n_streams <= 64u * (size_t)std::max(p->tab.cu_count, 1);
-  // the probe also serves an explicit RX_KERNEL_SYM_PACK: whether look-ahead pruning pays depends on the input
-  const bool probe_for_pack = kernel == RX_KERNEL_SYM_PACK && p->tab.symidx_p && p->opts.collect_stats == 0;
-  if ((kernel == RX_KERNEL_AUTO || probe_for_pack) && !pair && !p->have_init) {
-    if (!p->auto_decided && !may_probe) {
-      p->auto_kernel = RX_KERNEL_SYM_PACK;
-      p->auto_lanes = 16;
-      p->auto_prune = p->auto_fold = p->probe_prune = false;
-      p->auto_reg_skip = p->tab.pin_tab != nullptr;
-      p->auto_decided = true;
-    }
-    if (!p->auto_decided) {
+  } else if ((kernel == RX_KERNEL_AUTO || (kernel == RX_KERNEL_SYM_PACK && p->tab.symidx_p && o.collect_stats == 0)) &&
+             !pair && !p->have_init) {
+    // (more streams, but at most 16 wavefronts of them per SIMD: the probe times both kernels on the batch)
+    const bool reg_eligible = kernel == RX_KERNEL_AUTO && reg_ok && p->n_streams <= 64u * (size_t)std::max(p->tab.cu_count, 1);
+    if (!p->auto_decided && may_probe) {
       if ((rc = auto_probe(p, reg_eligible))) return rc;
-      p->auto_decided = true;
-      store_choice(p, p->tuning);
-      if (p->opts.flags & RX_OPT_VERBOSE)
+      ch.pinned = p->tuning;
+      p->choices[p->shape_key] = ch;
+      if (o.flags & RX_OPT_VERBOSE)
         fprintf(stderr, "[rxmatch] AUTO -> kernel %u, %u streams per wavefront, look-ahead pruning %s, folding %s\n",
-                p->auto_kernel, p->auto_lanes, p->auto_prune ? "on" : "off", p->auto_fold ? "on" : "off");
+                ch.kernel, ch.lanes, ch.prune ? "on" : "off", ch.fold ? "on" : "off");
+    } else if (!p->auto_decided) {
+      ch.kernel = RX_KERNEL_SYM_PACK;
+      ch.lanes = 16;
+      ch.prune = ch.fold = ch.probe_prune = false;
+      ch.reg_skip = p->tab.pin_tab != nullptr;
     }
-    if (kernel == RX_KERNEL_AUTO) {
-      kernel = p->auto_kernel;
-      if (p->opts.group_lanes == 0 && kernel == RX_KERNEL_SYM_PACK) auto_lanes = p->auto_lanes;
-    }
+    p->auto_decided = true;
+    if (kernel == RX_KERNEL_AUTO) kernel = ch.kernel;
   }
+  *out = kernel;
+  return RX_OK;
+}
+
+// The launch configuration p->cfg for decide_kernel's kernel, from the options, AUTO's choice and the tables the
+// automaton has (rx_pick_launch also fills the geometry fields of p->params)
+static int resolve_cfg(rx_plan* p, uint32_t kernel) {
+  const rx_opts& o = p->opts;
+  const rx_plan::AutoChoice& ch = p->choice;
+  const bool by_auto = o.kernel == RX_KERNEL_AUTO;
+  RxLaunchCfg& c = p->cfg;
   // a caller-supplied start set is a bitmask row: that is the wave kernel's dense form
   if (p->have_init && (kernel == RX_KERNEL_AUTO || kernel == RX_KERNEL_SYM_GROUP || kernel == RX_KERNEL_SYM_PACK ||
                        kernel == RX_KERNEL_DFA || kernel == RX_KERNEL_SYM_REG))
     kernel = RX_KERNEL_SYM_WAVE;
-  if (kernel == RX_KERNEL_SYM_REG && (p->opts.collect_stats != 0 || !p->tab.regidx)) kernel = RX_KERNEL_SYM_WAVE;
-  p->cfg.group_lanes = auto_lanes ? auto_lanes : p->opts.group_lanes;
-  rc = rx_pick_launch(kernel, h.size, a.n_streams, p->tab.cu_count, p->tab.lds_per_cu, &a, &p->cfg);
+  if (kernel == RX_KERNEL_SYM_REG && (o.collect_stats != 0 || !p->tab.regidx)) kernel = RX_KERNEL_SYM_WAVE;
+  // streams per wavefront: AUTO's when it chose the pack kernel (the pair build is not its choice), unless the caller named them
+  const bool auto_pack = by_auto && o.collect_stats != 2 && kernel == RX_KERNEL_SYM_PACK;
+  c.group_lanes = auto_pack && o.group_lanes == 0 ? ch.lanes : o.group_lanes;
+  const int rc = rx_pick_launch(kernel, p->nfa->h.size, p->params.n_streams, p->tab.cu_count, p->tab.lds_per_cu, &p->params, &c);
   if (rc) return rc;
-  p->cfg.stats = p->opts.collect_stats != 0;
-  // always-on-state folding: AUTO's verified choice; an explicit RX_KERNEL_SYM_PACK folds only on RX_OPT_FORCE_FOLD (its
-  // group_lanes then names one of the FOLD builds: 8/13/16/24/32/48/64 streams per wavefront)
-  p->cfg.fold = p->tab.pin_tab != nullptr && !p->cfg.stats && !p->have_init && !(p->opts.flags & RX_OPT_NO_FOLD) &&
-                ((p->cfg.kernel == RX_KERNEL_SYM_PACK &&
-                  ((p->opts.flags & RX_OPT_FORCE_FOLD) != 0 || (p->opts.kernel == RX_KERNEL_AUTO && p->auto_fold))) ||
-                 p->cfg.kernel == RX_KERNEL_SYM_REG);  // the register kernel folds whenever the automaton allows
-  if (p->cfg.kernel == RX_KERNEL_SYM_REG)
-    p->cfg.fold = p->tab.pin_tab != nullptr;  // (their index is built for exactly that)
-  if (p->cfg.fold && p->cfg.kernel == RX_KERNEL_SYM_PACK) {
+  c.stats = o.collect_stats != 0;
+  // always-on-state folding: the register kernel folds whenever the automaton allows (its index is built for exactly that);
+  // the pack kernel on AUTO's verified choice or on RX_OPT_FORCE_FOLD (an explicit RX_KERNEL_SYM_PACK's group_lanes then
+  // names one of the FOLD builds: 8/13/16/24/32/48/64 streams per wavefront)
+  const bool has_pin = p->tab.pin_tab != nullptr;
+  if (c.kernel == RX_KERNEL_SYM_REG)
+    c.fold = has_pin;
+  else
+    c.fold = has_pin && c.kernel == RX_KERNEL_SYM_PACK && !c.stats && !(o.flags & RX_OPT_NO_FOLD) &&
+             ((o.flags & RX_OPT_FORCE_FOLD) != 0 || (by_auto && ch.fold));
+  if (c.fold && c.kernel == RX_KERNEL_SYM_PACK) {
     static const uint32_t fold_s[] = {8, 13, 16, 24, 32, 48, 64};
     uint32_t pick = 64;
-    for (uint32_t c : fold_s) if (p->cfg.group_lanes <= c) { pick = c; break; }
-    p->cfg.group_lanes = pick;
-  } else if (p->cfg.kernel == RX_KERNEL_SYM_PACK && p->cfg.group_lanes > 32) {
-    p->cfg.group_lanes = 32;
+    for (uint32_t s : fold_s) if (c.group_lanes <= s) { pick = s; break; }
+    c.group_lanes = pick;
+  } else if (c.kernel == RX_KERNEL_SYM_PACK && c.group_lanes > 32) {
+    c.group_lanes = 32;
   }
-  p->cfg.verbose = (p->opts.flags & RX_OPT_VERBOSE) != 0;
-  p->cfg.profile_pack = (p->opts.flags & RX_OPT_PROFILE_PACK) != 0;
-  p->cfg.reg_skip = !(p->opts.flags & RX_OPT_REG_NO_SKIP) && (p->opts.kernel == RX_KERNEL_AUTO ? p->auto_reg_skip : true);
+  c.verbose = (o.flags & RX_OPT_VERBOSE) != 0;
+  c.profile_pack = (o.flags & RX_OPT_PROFILE_PACK) != 0;
+  c.reg_skip = !(o.flags & RX_OPT_REG_NO_SKIP) && (!by_auto || ch.reg_skip);
   // look-ahead pruning of multi-target rows follows the probe: AUTO's verified choice, or for an explicit
   // RX_KERNEL_SYM_PACK what the probe's statistics say.  rx_opts.flags RX_OPT_NO_PRUNE / RX_OPT_FORCE_PRUNE override it
   // (A/B measurements; tests, whose batches are too small for a probe).
-  p->cfg.prune = p->tab.symidx_p != nullptr && !(p->opts.flags & RX_OPT_NO_PRUNE) &&
-                 ((p->opts.flags & RX_OPT_FORCE_PRUNE) != 0 ||
-                  (p->opts.kernel == RX_KERNEL_SYM_PACK ? p->probe_prune : p->opts.kernel == RX_KERNEL_AUTO && p->auto_prune));
-  const bool two_tier = p->cfg.kernel == RX_KERNEL_SYM_GROUP || p->cfg.kernel == RX_KERNEL_SYM_PACK ||
-                        p->cfg.kernel == RX_KERNEL_DFA || p->cfg.kernel == RX_KERNEL_SYM_REG;
-  if (two_tier && (rc = ensure_spill_area(p, a))) return rc;
+  c.prune = p->tab.symidx_p != nullptr && !(o.flags & RX_OPT_NO_PRUNE) &&
+            ((o.flags & RX_OPT_FORCE_PRUNE) != 0 ||
+             (o.kernel == RX_KERNEL_SYM_PACK ? ch.probe_prune : by_auto && ch.prune));
+  return RX_OK;
+}
+
+// the kernels that hand the streams their lists cannot hold to the wave kernel: two launches
+static bool two_tier(uint32_t kernel) {
+  return kernel == RX_KERNEL_SYM_GROUP || kernel == RX_KERNEL_SYM_PACK || kernel == RX_KERNEL_DFA || kernel == RX_KERNEL_SYM_REG;
+}
+
+// Everything a launch decides before anything is enqueued for it: kernel arguments for the whole batch (p->params),
+// kernel choice (AUTO's probe runs here when its decision is not valid for the batch) and launch geometry (p->cfg).
+static int prepare_launch(rx_plan* p) {
+  uint32_t kernel = 0;
+  int rc;
+  if ((rc = batch_params(p)) || (rc = decide_kernel(p, &kernel)) || (rc = resolve_cfg(p, kernel))) return rc;
+  RxParams& a = p->params;
+  if (two_tier(p->cfg.kernel) && (rc = ensure_spill_area(p, a))) return rc;
   if (p->cfg.kernel == RX_KERNEL_DFA) {
-    if (pair) return RX_EINVAL;
     DevTables t;
     if ((rc = ensure_dfa_tables(p->nfa, p->device, &t))) return rc;
     a.dfa_trans = t.dfa_trans;
@@ -1113,31 +1117,30 @@ extern "C" int rx_plan_launch(rx_plan* p) {
   // the plan's creation, a reset enqueued here); this launch's kernel zeroes the one after
   const size_t set_words = 16 + (size_t)h.size;
   if (!p->sets_clean) {
-    for (int q = 0; q < 2; q++) HIPCHK(hipMemsetAsync(p->d_cset[q], 0, set_words * sizeof(unsigned long long), p->stream));
+    for (auto& set : p->d_cset) HIPCHK(hipMemsetAsync(set.p, 0, set_words * sizeof(unsigned long long), p->stream));
     p->sets_clean = true;
   }
   p->cur_set ^= 1;
-  p->d_counters = p->d_cset[p->cur_set];
+  p->d_counters = p->d_cset[p->cur_set].p;
   p->d_mct = p->d_counters + 16;
   a.counters = p->d_counters;
   a.ev_count = p->d_counters;
   a.match_count_total = p->d_mct;
   if (a.spill_count) a.spill_count = p->d_counters + 3;
-  a.zero_next = p->d_cset[p->cur_set ^ 1];
+  a.zero_next = p->d_cset[p->cur_set ^ 1].p;
   a.zero_words = (uint32_t)set_words;
-  if (p->want_mc) HIPCHK(hipMemsetAsync(p->d_mc, 0, p->n_streams * h.size * sizeof(uint32_t), p->stream));
+  if (p->want_mc) HIPCHK(hipMemsetAsync(p->d_mc.p, 0, p->n_streams * h.size * sizeof(uint32_t), p->stream));
   if (p->n_timed >= 4096) p->n_timed = 0;  // nobody is reading the times: recycle the pool
   if (p->n_timed == p->evs.size()) {
-    hipEvent_t a0 = nullptr, a1 = nullptr;
-    HIPCHK(hipEventCreate(&a0));
-    HIPCHK(hipEventCreate(&a1));
-    p->evs.emplace_back(a0, a1);
+    std::pair<HipEvent, HipEvent> ev;
+    if ((rc = ev.first.create()) || (rc = ev.second.create())) return rc;
+    p->evs.push_back(std::move(ev));
   }
   auto& ev = p->evs[p->n_timed];
-  HIPCHK(hipEventRecord(ev.first, p->stream));  // brackets the match kernel(s) only, on their own stream
+  HIPCHK(hipEventRecord(ev.first.e, p->stream));  // brackets the match kernel(s) only, on their own stream
   hipError_t e = (hipError_t)rx_launch(a, p->cfg, p->stream);
   if (e != hipSuccess) return hip_fail(e, "kernel launch");
-  HIPCHK(hipEventRecord(ev.second, p->stream));
+  HIPCHK(hipEventRecord(ev.second.e, p->stream));
   p->n_timed++;
   p->launched = true;
   return RX_OK;
@@ -1161,10 +1164,10 @@ extern "C" int rx_plan_tune(rx_plan* p) {
   p->tuning = false;
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(p->stream));
-  if (p->opts.kernel != RX_KERNEL_AUTO && !p->choices.count(p->shape_key)) store_choice(p, true);  // (nothing to decide: pin the no-op)
+  p->choice.pinned = true;
   auto it = p->choices.find(p->shape_key);
   if (it != p->choices.end()) it->second.pinned = true;
-  p->choice_pinned = true;
+  else if (p->opts.kernel != RX_KERNEL_AUTO) p->choices[p->shape_key] = p->choice;  // (nothing to decide: pin the no-op)
   return RX_OK;
   RX_CATCH
 }
@@ -1193,9 +1196,9 @@ extern "C" int rx_plan_kernel_times(rx_plan* p, uint32_t* n_launches, double* su
   if (!p) return RX_EINVAL;
   double sum = 0, mn = 0, mx = 0;
   for (size_t i = 0; i < p->n_timed; i++) {
-    HIPCHK(hipEventSynchronize(p->evs[i].second));
+    HIPCHK(hipEventSynchronize(p->evs[i].second.e));
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, p->evs[i].first, p->evs[i].second));
+    HIPCHK(hipEventElapsedTime(&ms, p->evs[i].first.e, p->evs[i].second.e));
     sum += ms;
     mn = i == 0 ? ms : std::min<double>(mn, ms);
     mx = std::max<double>(mx, ms);
@@ -1215,9 +1218,9 @@ extern "C" int rx_plan_sync(rx_plan* p, double* kernel_ms) {
   if (!p->launched) return RX_ESTATE;
   if (p->n_timed == 0) { if (kernel_ms) *kernel_ms = p->last_ms; return RX_OK; }
   auto& ev = p->evs[p->n_timed - 1];
-  HIPCHK(hipEventSynchronize(ev.second));
+  HIPCHK(hipEventSynchronize(ev.second.e));
   float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, ev.first, ev.second));
+  HIPCHK(hipEventElapsedTime(&ms, ev.first.e, ev.second.e));
   p->last_ms = ms;
   if (kernel_ms) *kernel_ms = ms;
   return RX_OK;
@@ -1268,31 +1271,27 @@ static void sort_events_into(const rx_event* src, rx_event* dst, size_t n, uint3
   }
 }
 
-static void sort_events(rx_event* ev, size_t n, uint32_t lo, size_t n_streams, std::vector<rx_event>& scratch) {
-  if (n < 2) return;
-  if (n < 64 || n_streams > 8 * n + 1024) { std::sort(ev, ev + n, ev_less); return; }
-  std::vector<uint32_t> at(n_streams + 1, 0u);
-  for (size_t i = 0; i < n; i++) {
-    const rx_event& e = ev[i];
-    if (e.stream < lo || e.stream - lo >= n_streams) { std::sort(ev, ev + n, ev_less); return; }  // not ours: be safe
-    at[e.stream - lo + 1]++;
-  }
-  for (size_t i = 0; i < n_streams; i++) at[i + 1] += at[i];
-  scratch.resize(n);
-  {
-    std::vector<uint32_t> pos(at.begin(), at.end() - 1);
-    for (size_t i = 0; i < n; i++) scratch[pos[ev[i].stream - lo]++] = ev[i];
-  }
-  for (size_t st = 0; st < n_streams; st++) {
-    const uint32_t b = at[st], e = at[st + 1];
-    for (uint32_t i = b + 1; i < e; i++) {
-      const rx_event x = scratch[i];
-      uint32_t j = i;
-      while (j > b && ev_less(x, scratch[j - 1])) { scratch[j] = scratch[j - 1]; j--; }
-      scratch[j] = x;
-    }
-  }
-  memcpy(ev, scratch.data(), n * sizeof(rx_event));
+// kernel_used, lanes_used and variant: what the plan's launch configuration ran
+static void stats_config(const rx_plan* p, rx_stats& st) {
+  const RxLaunchCfg& c = p->cfg;
+  st.kernel_used = c.kernel;
+  st.lanes_used = (c.kernel == RX_KERNEL_SYM_GROUP || c.kernel == RX_KERNEL_SYM_PACK) ? c.group_lanes : 0u;
+  st.variant = (c.stats ? RX_VARIANT_STATS : 0u) |
+               (c.kernel == RX_KERNEL_SYM_PACK && c.prune && !c.stats && p->tab.symidx_p ? RX_VARIANT_PRUNE : 0u) |
+               (c.fold ? RX_VARIANT_FOLD : 0u);
+}
+
+// alg_bytes and tb_cycles (statistics build) from the counter sums in `st`, the streams handed off and the pairs' clock cost
+static void stats_traffic(const rx_plan* p, rx_stats& st, unsigned long long spilled, unsigned long long pair_cost) {
+  if (!p->cfg.stats) return;
+  // 1 B per consumed byte + 8 B per active state + 4 B per edge of its row
+  // + 1 bit per pass (per stream, rounded up to bytes) + 12 B per accept event
+  st.alg_bytes = (uint64_t)p->params.n_consume * p->n_streams + 8 * st.sum_active + 4 * st.sum_edges +
+                 (uint64_t)p->n_streams * ((st.n_passes + 7) / 8) + 12 * st.n_events;
+  // per pair 1 reset clock + per pass [size + sum over states active in either stream of
+  // (cost - 1)].  Only defined if no stream left the pack kernel.
+  if (p->params.pair_cycles && spilled == 0)
+    st.tb_cycles = (p->n_streams / 2) * (1 + (uint64_t)p->params.n_consume * p->nfa->h.size) + pair_cost;
 }
 
 // rx_result as the caller's version of the header laid it out (see read_opts)
@@ -1346,34 +1345,22 @@ static int plan_download(rx_plan* p, rx_result* res) {
   st.n_passes = p->params.n_passes;
   st.n_events = cnt[0];
   st.kernel_ms = p->last_ms;
-  st.kernel_used = p->cfg.kernel;
-  st.lanes_used = (p->cfg.kernel == RX_KERNEL_SYM_GROUP || p->cfg.kernel == RX_KERNEL_SYM_PACK) ? p->cfg.group_lanes : 0u;
-  st.variant = (p->cfg.stats ? RX_VARIANT_STATS : 0u) |
-               (p->cfg.kernel == RX_KERNEL_SYM_PACK && p->cfg.prune && !p->cfg.stats && p->tab.symidx_p ? RX_VARIANT_PRUNE : 0u) |
-               (p->cfg.fold ? RX_VARIANT_FOLD : 0u);
-  st.n_launches = (p->cfg.kernel == RX_KERNEL_SYM_GROUP || p->cfg.kernel == RX_KERNEL_SYM_PACK ||
-                   p->cfg.kernel == RX_KERNEL_DFA || p->cfg.kernel == RX_KERNEL_SYM_REG) ? 2 : 1;
+  stats_config(p, st);
+  st.n_launches = two_tier(p->cfg.kernel) ? 2 : 1;
   if (p->cfg.stats) {
     st.sum_active = cnt[1];
     st.sum_edges = cnt[2];
-    // 1 B per consumed byte + 8 B per active state + 4 B per edge of its row
-    // + 1 bit per pass (per stream, rounded up to bytes) + 12 B per accept event
-    st.alg_bytes = (uint64_t)p->params.n_consume * p->n_streams + 8 * st.sum_active + 4 * st.sum_edges +
-                   (uint64_t)p->n_streams * ((st.n_passes + 7) / 8) + 12 * st.n_events;
-    // per pair 1 reset clock + per pass [size + sum over states active in either stream of
-    // (cost - 1)].  Only defined if no stream left the pack kernel (cnt[3] = handed-off streams).
-    if (p->params.pair_cycles && cnt[3] == 0)
-      st.tb_cycles = (p->n_streams / 2) * (1 + (uint64_t)p->params.n_consume * h.size) + cnt[4];
   }
+  stats_traffic(p, st, cnt[3], cnt[4]);  // (cnt[3]: streams handed off)
   const size_t captured = (size_t)std::min<unsigned long long>(cnt[0], p->events_cap);
   res->events_overflow = cnt[0] > p->events_cap ? 1u : 0u;
   res->n_events = 0;
   if (res->events && res->events_cap && captured) {
-    std::vector<rx_event> tmp(captured), scratch;
-    HIPCHK(hipMemcpy(tmp.data(), p->d_events, captured * sizeof(rx_event), hipMemcpyDeviceToHost));
-    sort_events(tmp.data(), tmp.size(), p->params.stream_base, p->n_streams, scratch);  // device order is arrival order; canonical = (stream,k,state)
+    std::vector<rx_event> tmp(captured), sorted(captured);
+    HIPCHK(hipMemcpy(tmp.data(), p->d_events.p, captured * sizeof(rx_event), hipMemcpyDeviceToHost));
+    sort_events_into(tmp.data(), sorted.data(), captured, p->params.stream_base, p->n_streams);  // device order is arrival order; canonical = (stream,k,state)
     const size_t n = std::min(captured, res->events_cap);
-    memcpy(res->events, tmp.data(), n * sizeof(rx_event));
+    memcpy(res->events, sorted.data(), n * sizeof(rx_event));
     res->n_events = n;
     if (captured > res->events_cap) res->events_overflow = 1u;
   } else if (cnt[0] && (!res->events || !res->events_cap)) {
@@ -1381,7 +1368,7 @@ static int plan_download(rx_plan* p, rx_result* res) {
   }
   if (res->match_count) {
     if (!p->want_mc) return RX_ESTATE;
-    HIPCHK(hipMemcpy(res->match_count, p->d_mc, p->n_streams * h.size * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(res->match_count, p->d_mc.p, p->n_streams * h.size * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
   if (res->match_count_total)
     HIPCHK(hipMemcpy(res->match_count_total, p->d_mct, (size_t)h.size * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -1390,14 +1377,14 @@ static int plan_download(rx_plan* p, rx_result* res) {
     const size_t need = (size_t)((st.n_passes + 31) / 32);
     if (res->anymatch_stride < need) return RX_EINVAL;
     if (need && res->anymatch_stride == p->am_stride)  // same pitch on both sides: one flat copy (2-D copies go row by row)
-      HIPCHK(hipMemcpy(res->anymatch, p->d_am, p->n_streams * p->am_stride * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(res->anymatch, p->d_am.p, p->n_streams * p->am_stride * 4, hipMemcpyDeviceToHost));
     else if (need)
-      HIPCHK(hipMemcpy2D(res->anymatch, res->anymatch_stride * 4, p->d_am, p->am_stride * 4, need * 4, p->n_streams,
+      HIPCHK(hipMemcpy2D(res->anymatch, res->anymatch_stride * 4, p->d_am.p, p->am_stride * 4, need * 4, p->n_streams,
                          hipMemcpyDeviceToHost));
   }
   if (res->final_active) {
     if (!p->want_final) return RX_ESTATE;
-    HIPCHK(hipMemcpy(res->final_active, p->d_final, p->n_streams * p->params.nw64x2 * sizeof(uint32_t),
+    HIPCHK(hipMemcpy(res->final_active, p->d_final.p, p->n_streams * p->params.nw64x2 * sizeof(uint32_t),
                      hipMemcpyDeviceToHost));
   }
   return RX_OK;
@@ -1484,31 +1471,9 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   // a preceding rx_plan_launch may still be reading the plan's input and output buffers on the plan's own stream
   HIPCHK(hipStreamSynchronize(p->stream));
   if ((rc = set_batch(p, n_streams, stream_len, stride))) return rc;
-  if (compact) {
-    if (res->final_states_cap > p->fstates_cap) {
-      (void)hipFree(p->d_fstates);
-      p->d_fstates = nullptr;
-      p->fstates_cap = 0;
-      HIPCHK(hipMalloc((void**)&p->d_fstates, res->final_states_cap * sizeof(uint32_t)));
-      p->fstates_cap = res->final_states_cap;
-    }
-    if (!p->d_foff) {
-      HIPCHK(hipMalloc((void**)&p->d_foff, p->max_streams * sizeof(uint32_t)));
-      HIPCHK(hipMalloc((void**)&p->d_fcnt, p->max_streams * sizeof(uint32_t)));
-    }
-  }
-  // input buffer of the plan, rows at a 4-byte-aligned pitch
-  const size_t pitch = (stream_len + 3) & ~(size_t)3;
-  const size_t need = std::max<size_t>(n_streams * pitch, 4);
-  if (need > p->d_in_own_bytes) {
-    (void)hipFree(p->d_in_own);
-    p->d_in_own = nullptr;
-    p->d_in_own_bytes = 0;
-    HIPCHK(hipMalloc((void**)&p->d_in_own, need));
-    p->d_in_own_bytes = need;
-  }
-  p->d_in = p->d_in_own;
-  p->stride = pitch;
+  if (compact && ((rc = p->d_fstates.grow(res->final_states_cap)) || (rc = p->d_foff.grow(p->max_streams)) ||
+                  (rc = p->d_fcnt.grow(p->max_streams))))
+    return rc;
   // blocks of streams: 32 768 or more each (smaller launches leave SIMDs idle), at most EIGHT, sizes a multiple of
   // 1 024 (lock-step pairs stay together).  THREE HIP streams shared by all blocks: uploads, kernels, downloads — a copy
   // runs beside a kernel, the two copy directions share the link (measured on the MI355X box: 56 GB/s in either direction
@@ -1518,35 +1483,22 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   size_t per = (n_streams + n_blocks - 1) / n_blocks;
   per = (per + 1023) & ~(size_t)1023;
   n_blocks = (n_streams + per - 1) / per;
-  if (!p->s_in) {
-    HIPCHK(hipStreamCreateWithFlags(&p->s_in, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&p->s_k, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&p->s_out, hipStreamNonBlocking));
-  }
-  if (!p->d_run_ctr) {
-    HIPCHK(hipMalloc((void**)&p->d_run_ctr, (2 + 2 * MAX_BLOCKS) * sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc((void**)&p->h_run_ctr, (2 + 2 * MAX_BLOCKS) * sizeof(unsigned long long), hipHostMallocDefault));
-  }
+  for (hipStream_t* s : {&p->s_in, &p->s_k, &p->s_out})
+    if (!*s) HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+  if ((rc = p->d_run_ctr.grow(2 + 2 * MAX_BLOCKS)) || (rc = p->h_run_ctr.grow(2 + 2 * MAX_BLOCKS))) return rc;
   while (p->pipes.size() < n_blocks) {
-    rx_plan::Pipe q;
-    HIPCHK(hipMalloc((void**)&q.d_set, set_words * sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc((void**)&q.h_set, set_words * sizeof(unsigned long long), hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&q.up, hipEventDisableTiming));
-    HIPCHK(hipEventCreate(&q.k0));
-    HIPCHK(hipEventCreate(&q.k1));
-    p->pipes.push_back(q);
+    rx_plan::Pipe q;  // (what was made of it is freed with it when a part fails)
+    if ((rc = q.d_set.grow(set_words)) || (rc = q.h_set.grow(set_words)) || (rc = q.up.create(hipEventDisableTiming)) ||
+        (rc = q.k0.create()) || (rc = q.k1.create()))
+      return rc;
+    p->pipes.push_back(std::move(q));
   }
   auto upload = [&](size_t b) -> int {
-    const size_t s0 = b * per, cnt = std::min(per, n_streams - s0);
+    const size_t s0 = b * per;
     *enqueued = true;
-    if (stream_len) {
-      if (stride == pitch && stream_len == pitch)
-        HIPCHK(hipMemcpyAsync(p->d_in_own + s0 * pitch, bytes + s0 * stride, cnt * pitch, hipMemcpyHostToDevice, p->s_in));
-      else
-        HIPCHK(hipMemcpy2DAsync(p->d_in_own + s0 * pitch, pitch, bytes + s0 * stride, stride, stream_len, cnt, hipMemcpyHostToDevice,
-                                p->s_in));
-    }
-    HIPCHK(hipEventRecord(p->pipes[b].up, p->s_in));
+    const int r = upload_rows(p, bytes, stride, s0, std::min(per, n_streams - s0), p->s_in);
+    if (r) return r;
+    HIPCHK(hipEventRecord(p->pipes[b].up.e, p->s_in));
     return RX_OK;
   };
   // block 0 goes up first: AUTO's probe (when its decision is not valid for this batch) reads a corner of it
@@ -1555,35 +1507,34 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   if ((rc = prepare_launch(p))) return rc;
   HIPCHK(hipStreamSynchronize(p->stream));  // (the probe ran on the plan's own stream)
   const size_t am_need = (size_t)((p->params.n_passes + 31) / 32);
-  const bool two_tier = p->cfg.kernel == RX_KERNEL_SYM_GROUP || p->cfg.kernel == RX_KERNEL_SYM_PACK ||
-                        p->cfg.kernel == RX_KERNEL_DFA || p->cfg.kernel == RX_KERNEL_SYM_REG;
   for (size_t b = 1; b < n_blocks; b++)  // all uploads are queued before any download (both use the same link)
     if ((rc = upload(b))) return rc;
   // ONE capacity for the whole call: the blocks' kernels run one after the other on the kernel stream and take their
   // event slots from one counter over the plan's whole event buffer (and the compaction kernels theirs from one counter
   // over the caller-sized list buffer); a snapshot of both counters behind every block tells the host where the block's
   // part ends.  A call whose events all lie in one block loses none as long as the total fits.
-  HIPCHK(hipMemsetAsync(p->d_run_ctr, 0, (2 + 2 * MAX_BLOCKS) * sizeof(unsigned long long), p->s_k));
+  unsigned long long* const d_run_ctr = p->d_run_ctr.p;
+  HIPCHK(hipMemsetAsync(d_run_ctr, 0, (2 + 2 * MAX_BLOCKS) * sizeof(unsigned long long), p->s_k));
   for (size_t b = 0; b < n_blocks; b++) {
     rx_plan::Pipe& q = p->pipes[b];
     const size_t s0 = b * per, cnt = std::min(per, n_streams - s0);
     RxParams a = p->params;  // the block's view of the batch
     RxLaunchCfg cfg = p->cfg;
-    a.bytes = p->d_in_own + s0 * pitch;
+    a.bytes = p->d_in + s0 * p->stride;
     a.n_streams = (uint32_t)cnt;
     a.stream_base = (uint32_t)s0;
-    a.events = p->events_cap ? p->d_events : nullptr;
+    a.events = p->events_cap ? p->d_events.p : nullptr;
     a.events_cap = (uint32_t)p->events_cap;
-    a.ev_count = p->d_run_ctr;
-    a.counters = q.d_set;
-    a.match_count_total = q.d_set + 16;
+    a.ev_count = d_run_ctr;
+    a.counters = q.d_set.p;
+    a.match_count_total = q.d_set.p + 16;
     a.zero_next = nullptr;
     a.zero_words = 0;
     if (a.match_count) a.match_count += s0 * size;
     if (a.anymatch) a.anymatch += s0 * p->am_stride;
     if (a.final_active) a.final_active += s0 * (size_t)a.nw64x2;
-    if (two_tier) {
-      a.spill_count = q.d_set + 3;
+    if (two_tier(cfg.kernel)) {
+      a.spill_count = q.d_set.p + 3;
       a.spill_streams += s0;
       a.spill_k += s0;
       a.spill_rows += s0 * (size_t)a.nw64x2;
@@ -1591,50 +1542,50 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
     const uint32_t lanes = cfg.group_lanes;
     if ((rc = rx_pick_launch(cfg.kernel, size, a.n_streams, p->tab.cu_count, p->tab.lds_per_cu, &a, &cfg))) return rc;
     cfg.group_lanes = lanes;
-    HIPCHK(hipMemsetAsync(q.d_set, 0, set_words * sizeof(unsigned long long), p->s_k));
-    if (p->want_mc) HIPCHK(hipMemsetAsync(p->d_mc + s0 * size, 0, cnt * size * sizeof(uint32_t), p->s_k));
-    HIPCHK(hipStreamWaitEvent(p->s_k, q.up, 0));
-    HIPCHK(hipEventRecord(q.k0, p->s_k));
+    HIPCHK(hipMemsetAsync(q.d_set.p, 0, set_words * sizeof(unsigned long long), p->s_k));
+    if (p->want_mc) HIPCHK(hipMemsetAsync(p->d_mc.p + s0 * size, 0, cnt * size * sizeof(uint32_t), p->s_k));
+    HIPCHK(hipStreamWaitEvent(p->s_k, q.up.e, 0));
+    HIPCHK(hipEventRecord(q.k0.e, p->s_k));
     // compact final sets: the pack kernel (and the wave kernel behind it) writes the lists itself and builds no rows; the
     // other kernels leave rows, which a small kernel behind them turns into lists
     const bool direct = compact && cfg.kernel == RX_KERNEL_SYM_PACK;
     if (direct) {
-      a.fin_states = p->d_fstates;
+      a.fin_states = p->d_fstates.p;
       a.fin_cap = (uint32_t)res->final_states_cap;
-      a.fin_off = p->d_foff + s0;
-      a.fin_cnt = p->d_fcnt + s0;
-      a.fin_count = p->d_run_ctr + 1;
+      a.fin_off = p->d_foff.p + s0;
+      a.fin_cnt = p->d_fcnt.p + s0;
+      a.fin_count = d_run_ctr + 1;
     }
     hipError_t e = (hipError_t)rx_launch(a, cfg, p->s_k);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     if (compact && !direct) {  // the lists of all blocks share the caller's capacity; offsets are positions in the whole buffer
-      e = (hipError_t)rx_launch_final_compact(a.final_active, a.n_streams, a.nw64x2, p->d_fstates, (uint32_t)res->final_states_cap,
-                                              p->d_foff + s0, p->d_fcnt + s0, p->d_run_ctr + 1, p->s_k);
+      e = (hipError_t)rx_launch_final_compact(a.final_active, a.n_streams, a.nw64x2, p->d_fstates.p, (uint32_t)res->final_states_cap,
+                                              p->d_foff.p + s0, p->d_fcnt.p + s0, d_run_ctr + 1, p->s_k);
       if (e != hipSuccess) return hip_fail(e, "final-set compaction launch");
     }
-    HIPCHK(hipMemcpyAsync(p->d_run_ctr + 2 + b, p->d_run_ctr, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->s_k));
-    HIPCHK(hipMemcpyAsync(p->d_run_ctr + 2 + MAX_BLOCKS + b, p->d_run_ctr + 1, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->s_k));
-    HIPCHK(hipEventRecord(q.k1, p->s_k));
+    HIPCHK(hipMemcpyAsync(d_run_ctr + 2 + b, d_run_ctr, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->s_k));
+    HIPCHK(hipMemcpyAsync(d_run_ctr + 2 + MAX_BLOCKS + b, d_run_ctr + 1, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->s_k));
+    HIPCHK(hipEventRecord(q.k1.e, p->s_k));
     // results of the block straight into the caller's arrays
-    HIPCHK(hipStreamWaitEvent(p->s_out, q.k1, 0));
-    HIPCHK(hipMemcpyAsync(q.h_set, q.d_set, set_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->s_out));
+    HIPCHK(hipStreamWaitEvent(p->s_out, q.k1.e, 0));
+    HIPCHK(hipMemcpyAsync(q.h_set.p, q.d_set.p, set_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->s_out));
     if (res->final_active)
-      HIPCHK(hipMemcpyAsync(res->final_active + s0 * nw64, p->d_final + s0 * (size_t)a.nw64x2, cnt * nw64 * sizeof(uint64_t),
+      HIPCHK(hipMemcpyAsync(res->final_active + s0 * nw64, p->d_final.p + s0 * (size_t)a.nw64x2, cnt * nw64 * sizeof(uint64_t),
                             hipMemcpyDeviceToHost, p->s_out));
     if (compact) {
-      HIPCHK(hipMemcpyAsync(res->final_off + s0, p->d_foff + s0, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->s_out));
-      HIPCHK(hipMemcpyAsync(res->final_cnt + s0, p->d_fcnt + s0, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->s_out));
+      HIPCHK(hipMemcpyAsync(res->final_off + s0, p->d_foff.p + s0, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->s_out));
+      HIPCHK(hipMemcpyAsync(res->final_cnt + s0, p->d_fcnt.p + s0, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, p->s_out));
     }
     if (res->anymatch && am_need) {
       if (res->anymatch_stride == p->am_stride)  // same pitch on both sides: one flat copy (2-D copies go row by row)
-        HIPCHK(hipMemcpyAsync(res->anymatch + s0 * p->am_stride, p->d_am + s0 * p->am_stride, cnt * p->am_stride * 4,
+        HIPCHK(hipMemcpyAsync(res->anymatch + s0 * p->am_stride, p->d_am.p + s0 * p->am_stride, cnt * p->am_stride * 4,
                               hipMemcpyDeviceToHost, p->s_out));
       else
-        HIPCHK(hipMemcpy2DAsync(res->anymatch + s0 * res->anymatch_stride, res->anymatch_stride * 4, p->d_am + s0 * p->am_stride,
+        HIPCHK(hipMemcpy2DAsync(res->anymatch + s0 * res->anymatch_stride, res->anymatch_stride * 4, p->d_am.p + s0 * p->am_stride,
                                 p->am_stride * 4, am_need * 4, cnt, hipMemcpyDeviceToHost, p->s_out));
     }
     if (res->match_count)
-      HIPCHK(hipMemcpyAsync(res->match_count + s0 * size, p->d_mc + s0 * size, cnt * size * sizeof(uint32_t), hipMemcpyDeviceToHost,
+      HIPCHK(hipMemcpyAsync(res->match_count + s0 * size, p->d_mc.p + s0 * size, cnt * size * sizeof(uint32_t), hipMemcpyDeviceToHost,
                             p->s_out));
     // (test hook, RX_OPT_INJECT_RUN_FAULT: fail here, with block 0's kernels and copies in flight)
     if (b == 0 && (p->opts.flags & RX_OPT_INJECT_RUN_FAULT)) {
@@ -1643,7 +1594,7 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
     }
   }
   // the counters and their per-block snapshots (the last block's k1 orders this copy behind every kernel)
-  HIPCHK(hipMemcpyAsync(p->h_run_ctr, p->d_run_ctr, (2 + 2 * MAX_BLOCKS) * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->s_out));
+  HIPCHK(hipMemcpyAsync(p->h_run_ctr.p, d_run_ctr, (2 + 2 * MAX_BLOCKS) * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->s_out));
   const bool verbose = (p->opts.flags & RX_OPT_VERBOSE) != 0;
   const auto w_issued = std::chrono::steady_clock::now();
   HIPCHK(hipStreamSynchronize(p->s_out));
@@ -1654,11 +1605,7 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   rx_stats& st = res->stats;
   st = rx_stats{};
   st.n_passes = p->params.n_passes;
-  st.kernel_used = p->cfg.kernel;
-  st.lanes_used = (p->cfg.kernel == RX_KERNEL_SYM_GROUP || p->cfg.kernel == RX_KERNEL_SYM_PACK) ? p->cfg.group_lanes : 0u;
-  st.variant = (p->cfg.stats ? RX_VARIANT_STATS : 0u) |
-               (p->cfg.kernel == RX_KERNEL_SYM_PACK && p->cfg.prune && !p->cfg.stats && p->tab.symidx_p ? RX_VARIANT_PRUNE : 0u) |
-               (p->cfg.fold ? RX_VARIANT_FOLD : 0u);
+  stats_config(p, st);
   res->n_events = 0;
   res->events_overflow = 0;
   if (res->match_count_total) memset(res->match_count_total, 0, (size_t)size * sizeof(uint64_t));
@@ -1666,10 +1613,10 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   for (size_t b = 0; b < n_blocks; b++) {
     rx_plan::Pipe& q = p->pipes[b];
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, q.k0, q.k1);
+    (void)hipEventElapsedTime(&ms, q.k0.e, q.k1.e);
     st.kernel_ms += ms;
-    st.n_launches += two_tier ? 2 : 1;
-    const unsigned long long* cnt = q.h_set;
+    st.n_launches += two_tier(p->cfg.kernel) ? 2 : 1;
+    const unsigned long long* cnt = q.h_set.p;
     st.sum_active += cnt[1];
     st.sum_edges += cnt[2];
     spilled += cnt[3];
@@ -1677,60 +1624,45 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
     if (res->match_count_total)
       for (uint32_t i = 0; i < size; i++) res->match_count_total[i] += cnt[16 + i];
   }
-  const unsigned long long* ev_after = p->h_run_ctr + 2;  // accept events of blocks 0..b
-  const unsigned long long ev_total = p->h_run_ctr[0];
+  const unsigned long long* ev_after = p->h_run_ctr.p + 2;  // accept events of blocks 0..b
+  const unsigned long long ev_total = p->h_run_ctr.p[0];
   st.n_events = ev_total;
   if (ev_total > p->events_cap && res->events) res->events_overflow = 1u;
   const size_t captured = (size_t)std::min<unsigned long long>(ev_total, p->events_cap);
   // The two downloads whose sizes the host has only now: both go out together, into page-locked staging (a blocking copy
   // into the caller's pageable arrays, one after the other, was 0.3 of the 2.5 ms of a configs[2] call); the events are put
   // into order on their way from the staging buffer to the caller's array.
-  auto stage = [](void** buf, size_t* have, size_t need) -> int {
-    if (need <= *have) return RX_OK;
-    if (*buf) (void)hipHostFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    const size_t want = need + need / 2;
-    HIPCHK(hipHostMalloc(buf, want, hipHostMallocDefault));
-    *have = want;
-    return RX_OK;
-  };
   const bool ev_down = res->events && res->events_cap && captured;
   size_t fs_n = 0;
   if (compact) {
     // (final_off is a position in final_states; a set that did not fit wholly is cut at the capacity, final_cnt stays exact)
-    const unsigned long long needed = p->h_run_ctr[1];
+    const unsigned long long needed = p->h_run_ctr.p[1];
     fs_n = (size_t)std::min<unsigned long long>(needed, res->final_states_cap);
     res->final_states_overflow = needed > res->final_states_cap ? 1u : 0u;
     res->n_final_states = fs_n;
   }
   if (ev_down) {
-    if ((rc = stage(&p->h_stage_ev, &p->h_stage_ev_bytes, captured * sizeof(rx_event)))) return rc;
-    HIPCHK(hipMemcpyAsync(p->h_stage_ev, p->d_events, captured * sizeof(rx_event), hipMemcpyDeviceToHost, p->s_out));
+    if ((rc = p->h_stage_ev.grow(captured, captured + captured / 2))) return rc;
+    HIPCHK(hipMemcpyAsync(p->h_stage_ev.p, p->d_events.p, captured * sizeof(rx_event), hipMemcpyDeviceToHost, p->s_out));
   }
   if (fs_n) {
-    if ((rc = stage(&p->h_stage_fs, &p->h_stage_fs_bytes, fs_n * sizeof(uint32_t)))) return rc;
-    HIPCHK(hipMemcpyAsync(p->h_stage_fs, p->d_fstates, fs_n * sizeof(uint32_t), hipMemcpyDeviceToHost, p->s_in));
+    if ((rc = p->h_stage_fs.grow(fs_n, fs_n + fs_n / 2))) return rc;
+    HIPCHK(hipMemcpyAsync(p->h_stage_fs.p, p->d_fstates.p, fs_n * sizeof(uint32_t), hipMemcpyDeviceToHost, p->s_in));
   }
   if (ev_down) {
     HIPCHK(hipStreamSynchronize(p->s_out));
     // the device buffer holds the blocks' events back to back in launch order (the first `captured` slots); each block's
-    // part is brought into (stream, k, state) order on its own (blocks are in stream order: the concatenation is sorted)
-    const rx_event* src = static_cast<const rx_event*>(p->h_stage_ev);
+    // part is brought into (stream, k, state) order on its own (blocks are in stream order: the concatenation is sorted).
+    // A caller's array shorter than what was captured gets the first n of the whole order.
     const size_t n = std::min(captured, res->events_cap);
-    if (n == captured) {
-      for (size_t b = 0; b < n_blocks; b++) {
-        const size_t lo = (size_t)std::min<unsigned long long>(b ? ev_after[b - 1] : 0ull, captured);
-        const size_t hi = (size_t)std::min<unsigned long long>(ev_after[b], captured);
-        if (hi > lo) sort_events_into(src + lo, res->events + lo, hi - lo, (uint32_t)(b * per), std::min(per, n_streams - b * per));
-      }
-    } else {  // the caller's array is shorter than what was captured: order everything, hand over the first n
-      std::vector<rx_event> tmp(src, src + captured), scratch;
-      for (size_t b = 0; b < n_blocks; b++) {
-        const size_t lo = (size_t)std::min<unsigned long long>(b ? ev_after[b - 1] : 0ull, captured);
-        const size_t hi = (size_t)std::min<unsigned long long>(ev_after[b], captured);
-        if (hi > lo) sort_events(tmp.data() + lo, hi - lo, (uint32_t)(b * per), std::min(per, n_streams - b * per), scratch);
-      }
+    std::vector<rx_event> tmp(n < captured ? captured : 0);
+    rx_event* dst = n < captured ? tmp.data() : res->events;
+    for (size_t b = 0; b < n_blocks; b++) {
+      const size_t lo = (size_t)std::min<unsigned long long>(b ? ev_after[b - 1] : 0ull, captured);
+      const size_t hi = (size_t)std::min<unsigned long long>(ev_after[b], captured);
+      if (hi > lo) sort_events_into(p->h_stage_ev.p + lo, dst + lo, hi - lo, (uint32_t)(b * per), std::min(per, n_streams - b * per));
+    }
+    if (n < captured) {
       memcpy(res->events, tmp.data(), n * sizeof(rx_event));
       res->events_overflow = 1u;
     }
@@ -1738,17 +1670,12 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   }
   if (fs_n) {
     HIPCHK(hipStreamSynchronize(p->s_in));
-    memcpy(res->final_states, p->h_stage_fs, fs_n * sizeof(uint32_t));
+    memcpy(res->final_states, p->h_stage_fs.p, fs_n * sizeof(uint32_t));
   }
   if (verbose)
     fprintf(stderr, "[rxmatch] run: events and final lists on the host %.3f ms after the last enqueue\n",
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w_issued).count());
-  if (p->cfg.stats) {
-    st.alg_bytes = (uint64_t)p->params.n_consume * n_streams + 8 * st.sum_active + 4 * st.sum_edges +
-                   (uint64_t)n_streams * ((st.n_passes + 7) / 8) + 12 * st.n_events;
-    if (p->params.pair_cycles && spilled == 0)
-      st.tb_cycles = (n_streams / 2) * (1 + (uint64_t)p->params.n_consume * size) + pair_cost;
-  }
+  stats_traffic(p, st, spilled, pair_cost);
   p->launched = false;  // (nothing is left on the device for rx_plan_download)
   p->sets_clean = false;
   return RX_OK;
