@@ -178,9 +178,10 @@ enum {
   RX_OPT_REG_NO_SKIP = 64u, /* SYM_REG: the build that does not step over passes in which no state is active (A/B runs) */
   RX_OPT_INJECT_RUN_FAULT = 128u, /* test hook: rx_plan_run fails with RX_EHIP once block 0's kernels and copies are in
                                      flight — exercises the drain-before-error-return path                           */
-  RX_OPT_NO_PROBE = 256u    /* RX_KERNEL_AUTO never probes inside rx_plan_launch / rx_plan_run: no sample launches, no
+  RX_OPT_NO_PROBE = 256u,   /* RX_KERNEL_AUTO never probes inside rx_plan_launch / rx_plan_run: no sample launches, no
                                timed candidates, no stream synchronisation.  The decision is the one rx_plan_tune made
                                for the shape, or a default (SYM_PACK, 16 streams per wavefront; SYM_REG up to 4 streams) */
+  RX_OPT_RAGGED_NO_SORT = 512u /* ragged batches: streams go to wavefront slots in the caller's order, not longest first (A/B) */
 };
 
 /* One accept pulse: `state` was active and accepting in pass `k` of stream `stream`.
@@ -206,7 +207,9 @@ typedef struct rx_stats {
                             (testbench_BLK_Mem.sv:84) prints for the pair(s), summed over pairs;
                             0 if unavailable                                               */
   /* ABI >= 2 (written only when the caller's rx_result.struct_size covers them) */
-  uint32_t lanes_used;   /* SYM_GROUP: lanes per stream; SYM_PACK: streams per wavefront; else 0 */
+  uint32_t lanes_used;   /* SYM_GROUP: lanes per stream; SYM_PACK: streams per wavefront (ragged batches: the S that ran,
+                            group_lanes mapped to the nearest of 4/8/11/13/16/22/24/32, FOLD builds as for
+                            uniform batches); else 0 */
   uint32_t variant;      /* RX_VARIANT_* bits of the build that ran                              */
 } rx_stats;
 enum {
@@ -257,6 +260,18 @@ typedef struct rx_result {
 int rx_match(const rx_nfa* nfa, const uint8_t* bytes, size_t n_streams, size_t stream_len,
              size_t stride, const uint64_t* init_active, const rx_opts* opts, rx_result* res);
 
+/* Ragged batch: stream s is bytes[offsets[s] .. offsets[s+1]) (offsets[0..n_streams], non-decreasing, a host array; lengths
+ * may be 0).  Every output of stream s equals what rx_match returns for that stream alone, renumbered to s: its own pass
+ * count (passes_for its length and the mode), events sorted by (stream, k, state), any-match bits at or beyond its own pass
+ * count 0 (anymatch_stride >= ceil(largest pass count / 32)), final_active = the set after its own last byte.  k_base stays
+ * global (checked against the longest stream).  stats: n_passes = the largest pass count; n_events, sum_active, sum_edges
+ * and alg_bytes summed over the streams.  Kernels: CSR_WAVE, SYM_WAVE, SYM_REG, SYM_PACK (plain, statistics, PRUNE and
+ * FOLD builds) and AUTO.  RX_EINVAL, before any device work, for decreasing offsets, collect_stats == 2, compact final
+ * lists, RX_KERNEL_SYM_GROUP / RX_KERNEL_DFA, RX_OPT_PROFILE_PACK.
+ * Non-pipelined: upload, launch, synchronise, download. */
+int rx_match_ragged(const rx_nfa* nfa, const uint8_t* bytes, const uint64_t* offsets, size_t n_streams,
+                    const uint64_t* init_active, const rx_opts* opts, rx_result* res);
+
 /* Same, streams split into contiguous blocks over n_devices GPUs (one host thread each, the
  * table replicated per device, no collective).  devices == NULL => ordinals 0..n_devices-1. */
 int rx_match_sharded(const rx_nfa* nfa, const uint8_t* bytes, size_t n_streams, size_t stream_len,
@@ -277,9 +292,17 @@ int rx_plan_upload(rx_plan* plan, const uint8_t* bytes, size_t n_streams, size_t
 /* Use a caller-owned DEVICE buffer as the input (e.g. a torch tensor's data_ptr). */
 int rx_plan_set_device_input(rx_plan* plan, const void* device_bytes, size_t n_streams,
                              size_t stream_len, size_t stride);
+/* Ragged batch (see rx_match_ragged) into the plan: the byte range bytes[offsets[0] .. offsets[n_streams]) in ONE copy, plus
+ * one descriptor per stream.  RX_EINVAL for decreasing offsets, a stream longer than the plan's max_stream_len, more than
+ * max_streams streams or max_streams * max_stream_len bytes, and for the options rx_match_ragged refuses.
+ * rx_plan_launch / rx_plan_tune / rx_plan_download / rx_plan_kernel_times work unchanged on it; rx_plan_run does not take it. */
+int rx_plan_upload_ragged(rx_plan* plan, const uint8_t* bytes, const uint64_t* offsets, size_t n_streams);
+/* The same over a caller-owned DEVICE buffer: stream s is device_bytes[offsets[s] .. offsets[s+1]); `offsets` is a HOST
+ * array (the plan orders the streams and chooses the kernel by their lengths). */
+int rx_plan_set_device_input_ragged(rx_plan* plan, const void* device_bytes, const uint64_t* offsets, size_t n_streams);
 /* Optional per-stream start state (host array; copied — bits beyond `size` cleared — before the call returns) for the
- * batch given last; every new input (rx_plan_upload / rx_plan_set_device_input / rx_plan_run) restores reset, and so
- * does NULL. */
+ * batch given last (rows by stream, also for a ragged batch); every new input (rx_plan_upload / rx_plan_set_device_input /
+ * rx_plan_upload_ragged / rx_plan_set_device_input_ragged / rx_plan_run) restores reset, and so does NULL. */
 int rx_plan_set_init_active(rx_plan* plan, const uint64_t* init_active);
 /* Enqueue result-reset + the match kernel on the plan's stream, bracketed by hipEvents.  With RX_KERNEL_AUTO the first
  * launch for a batch shape (and every 32nd of the same shape) first probes — sample launches and a stream synchronisation

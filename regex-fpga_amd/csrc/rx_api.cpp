@@ -432,6 +432,14 @@ struct rx_plan {
   size_t am_stride = 0;
   // current batch
   size_t n_streams = 0, stream_len = 0, stride = 0;
+  size_t batch_bytes = 0;      // input bytes of the batch (n_streams * stream_len for a uniform one)
+  // ragged batch (rx_plan_upload_ragged / rx_plan_set_device_input_ragged): stream_len is the longest stream's length and
+  // `slots` the descriptors in wavefront-slot order (longest first unless RX_OPT_RAGGED_NO_SORT), in HBM as d_slots;
+  // AUTO's probes take an even sample of them (probe_slots / d_probe_slots)
+  bool ragged = false;
+  std::vector<RxSlot> slots, probe_slots;
+  HipBuf<RxSlot> d_slots, d_probe_slots;
+  uint64_t ragged_consume = 0, ragged_am_bytes = 0;  // sums over the streams of the bytes consumed and of ceil(passes / 8)
   bool have_input = false, launched = false;
   bool auto_decided = false;   // RX_KERNEL_AUTO: `choice` is valid for the current batch
   uint32_t batches_since_probe = 0;
@@ -577,15 +585,12 @@ static uint32_t ceil_log2(size_t v) {
   return b;
 }
 
-static int set_batch(rx_plan* p, size_t n_streams, size_t stream_len, size_t stride) {
-  if (n_streams == 0 || n_streams > p->max_streams || stream_len > p->max_len || stride < stream_len)
-    return RX_EINVAL;
-  // AUTO's probe costs about as much as a launch.  Its decision is kept per shape bucket; a plan that is fed batch after
-  // batch of one shape (serving) looks again every 32nd batch — unless the decision was made by rx_plan_tune or the plan
-  // was created with RX_OPT_NO_PROBE.  A wrong guess only costs speed (hand-offs keep every kernel exact).
-  const bool same_shape = p->have_input && p->n_streams == n_streams && p->stream_len == stream_len;
+// AUTO's probe costs about as much as a launch.  Its decision is kept per shape bucket; a plan that is fed batch after
+// batch of one shape (serving) looks again every 32nd batch — unless the decision was made by rx_plan_tune or the plan
+// was created with RX_OPT_NO_PROBE.  A wrong guess only costs speed (hand-offs keep every kernel exact).
+static void enter_shape(rx_plan* p, bool same_shape, uint32_t key) {
   if (!same_shape) {
-    p->shape_key = (ceil_log2(n_streams) << 8) | ceil_log2(stream_len + 1);
+    p->shape_key = key;
     auto it = p->choices.find(p->shape_key);
     p->batches_since_probe = 0;
     if (it != p->choices.end()) {
@@ -599,6 +604,15 @@ static int set_batch(rx_plan* p, size_t n_streams, size_t stream_len, size_t str
     p->auto_decided = false;
     p->batches_since_probe = 0;
   }
+}
+
+static int set_batch(rx_plan* p, size_t n_streams, size_t stream_len, size_t stride) {
+  if (n_streams == 0 || n_streams > p->max_streams || stream_len > p->max_len || stride < stream_len)
+    return RX_EINVAL;
+  const bool same_shape = p->have_input && !p->ragged && p->n_streams == n_streams && p->stream_len == stream_len;
+  enter_shape(p, same_shape, (ceil_log2(n_streams) << 8) | ceil_log2(stream_len + 1));
+  p->ragged = false;
+  p->batch_bytes = n_streams * stream_len;
   p->n_streams = n_streams;
   p->stream_len = stream_len;
   p->stride = stride;
@@ -644,6 +658,106 @@ extern "C" int rx_plan_set_device_input(rx_plan* p, const void* device_bytes, si
   if (!p || (!device_bytes && stream_len)) return RX_EINVAL;
   int rc = set_batch(p, n_streams, stream_len, stride);
   if (rc) return rc;
+  p->d_in = (const uint8_t*)device_bytes;
+  return RX_OK;
+  RX_CATCH
+}
+
+// ---- ragged batches ---------------------------------------------------------------------------------
+// What a ragged batch cannot run with (rx_match_ragged, rx_plan_upload_ragged): the pair clock model needs equal lengths; the
+// group and DFA kernels and the pack kernel's stamped build have no ragged form.
+static bool ragged_opts_ok(const rx_opts& o) {
+  return o.mode <= RX_MODE_TB_COMPAT && o.collect_stats != 2 && o.kernel != RX_KERNEL_SYM_GROUP && o.kernel != RX_KERNEL_DFA &&
+         !(o.flags & RX_OPT_PROFILE_PACK);
+}
+
+// offsets[0..n] non-decreasing, no stream longer than `max_len`; *longest = the longest stream's length
+static bool ragged_offsets_ok(const uint64_t* offsets, size_t n, size_t max_len, size_t* longest) {
+  if (!offsets || n == 0) return false;
+  size_t mx = 0;
+  for (size_t s = 0; s < n; s++) {
+    if (offsets[s + 1] < offsets[s] || offsets[s + 1] - offsets[s] > max_len) return false;
+    mx = std::max<size_t>(mx, offsets[s + 1] - offsets[s]);
+  }
+  *longest = mx;
+  return true;
+}
+
+// The batch's descriptors (byte offsets from `base`), in wavefront-slot order, into HBM; shape bucket with the ragged bit.
+// `in_bytes` > 0: the plan's own input buffer is grown to that.  A refused batch (RX_EINVAL) leaves the plan as it was; once
+// buffers are grown or copies enqueued the plan holds no input until the call has succeeded (a failure leaves none).
+static int set_batch_ragged(rx_plan* p, const uint64_t* offsets, size_t n, uint64_t base, size_t in_bytes) {
+  size_t longest = 0;
+  if (n > p->max_streams || !ragged_opts_ok(p->opts) || !ragged_offsets_ok(offsets, n, p->max_len, &longest)) return RX_EINVAL;
+  const uint64_t total = offsets[n] - offsets[0];
+  if (total > (uint64_t)p->max_streams * p->max_len) return RX_EINVAL;
+  const bool same_kind = p->have_input && p->ragged;
+  p->have_input = false;
+  p->launched = false;
+  int rc;
+  if (in_bytes && (rc = p->d_in_own.grow(in_bytes))) return rc;
+  if ((rc = p->d_slots.grow(n))) return rc;
+  std::vector<uint32_t> order(n);
+  for (size_t s = 0; s < n; s++) order[s] = (uint32_t)s;
+  // longest first: the streams that share a pack wavefront end close together, and the longest start first
+  if (!(p->opts.flags & RX_OPT_RAGGED_NO_SORT))
+    std::stable_sort(order.begin(), order.end(),
+                     [offsets](uint32_t a, uint32_t b) { return offsets[a + 1] - offsets[a] > offsets[b + 1] - offsets[b]; });
+  p->slots.resize(n);
+  p->ragged_consume = p->ragged_am_bytes = 0;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t s = order[i];
+    const uint64_t len = offsets[s + 1] - offsets[s];
+    p->slots[i] = RxSlot{offsets[s] - base, (uint32_t)len, s};
+    const uint64_t passes = passes_for(len, p->opts.mode);
+    p->ragged_consume += p->opts.mode == RX_MODE_TB_COMPAT ? passes : len;
+    p->ragged_am_bytes += (passes + 7) / 8;
+  }
+  HIPCHK(hipMemcpyAsync(p->d_slots.p, p->slots.data(), n * sizeof(RxSlot), hipMemcpyHostToDevice, p->stream));
+  const size_t mean = (size_t)(total / n);
+  const uint32_t key = (1u << 31) | (ceil_log2(n) << 8) | ceil_log2(mean + 1);
+  enter_shape(p, same_kind && key == p->shape_key, key);
+  p->ragged = true;
+  p->batch_bytes = total;
+  p->n_streams = n;
+  p->stream_len = longest;
+  p->stride = 0;
+  p->have_input = true;
+  p->launched = false;
+  p->have_init = false;
+  return RX_OK;
+}
+
+extern "C" int rx_plan_upload_ragged(rx_plan* p, const uint8_t* bytes, const uint64_t* offsets, size_t n_streams) {
+  RX_TRY
+  if (!p || !offsets || n_streams == 0) return RX_EINVAL;
+  if (!bytes && offsets[n_streams] != offsets[0]) return RX_EINVAL;
+  int dev;
+  int rc = bind_device(p->device, &dev);
+  if (rc) return rc;
+  // the whole range in one copy; room up to the end of its last 16-byte granule (the pack kernel's loader reads granules)
+  const size_t total = (size_t)(offsets[n_streams] - offsets[0]);
+  if ((rc = set_batch_ragged(p, offsets, n_streams, offsets[0], ((total + 15) & ~(size_t)15) + 16))) return rc;
+  p->d_in = p->d_in_own.p;
+  if (total) {
+    const hipError_t e = hipMemcpyAsync(p->d_in_own.p, bytes + offsets[0], total, hipMemcpyHostToDevice, p->stream);
+    if (e != hipSuccess) {
+      p->have_input = false;  // (the descriptors are in place, the bytes are not)
+      return hip_fail(e, "hipMemcpyAsync (ragged input)");
+    }
+  }
+  return RX_OK;
+  RX_CATCH
+}
+
+extern "C" int rx_plan_set_device_input_ragged(rx_plan* p, const void* device_bytes, const uint64_t* offsets, size_t n_streams) {
+  RX_TRY
+  if (!p || !offsets || n_streams == 0) return RX_EINVAL;
+  if (!device_bytes && offsets[n_streams] != offsets[0]) return RX_EINVAL;
+  int dev;
+  int rc = bind_device(p->device, &dev);
+  if (rc) return rc;
+  if ((rc = set_batch_ragged(p, offsets, n_streams, 0, 0))) return rc;
   p->d_in = (const uint8_t*)device_bytes;
   return RX_OK;
   RX_CATCH
@@ -737,6 +851,31 @@ static int sample_launch(rx_plan* p, RxLaunchCfg want, size_t n_streams, size_t 
   a.stream_len = (uint32_t)len;
   a.n_passes = n_passes;
   a.n_consume = a.stream_len;
+  if (p->ragged) {
+    if (n_streams >= p->n_streams && len >= p->stream_len) {
+      a.slots = p->d_slots.p;  // the whole batch
+      a.stream_len = (uint32_t)p->stream_len;
+      a.n_consume = a.stream_len;
+    } else {
+      // n_streams slots spread evenly over the sorted order, each cut to `len` bytes
+      p->probe_slots.resize(n_streams);
+      uint32_t longest = 0;
+      for (size_t i = 0; i < n_streams; i++) {
+        RxSlot d = p->slots[i * p->n_streams / n_streams];
+        d.len = (uint32_t)std::min<size_t>(d.len, len);
+        d.id = (uint32_t)i;
+        p->probe_slots[i] = d;
+        longest = std::max(longest, d.len);
+      }
+      int rc = p->d_probe_slots.grow(n_streams);
+      if (rc) return rc;
+      HIPCHK(hipMemcpyAsync(p->d_probe_slots.p, p->probe_slots.data(), n_streams * sizeof(RxSlot), hipMemcpyHostToDevice, p->stream));
+      a.slots = p->d_probe_slots.p;
+      a.stream_len = longest;
+      a.n_consume = longest;
+    }
+    a.n_passes = n_passes > len ? a.n_consume + 1u : a.n_consume;  // (the mode the caller asked for)
+  }
   RxLaunchCfg cfg = want;
   int rc = rx_pick_launch(want.kernel, a.size, a.n_streams, p->tab.cu_count, p->tab.lds_per_cu, &a, &cfg);
   if (rc) return rc;
@@ -765,7 +904,7 @@ static int auto_probe_pack(rx_plan* p) {
   ch.fold = false;
   ch.probe_prune = false;
   ch.probe_active = 0;
-  if (p->n_streams * p->stream_len < (256u << 10)) return RX_OK;  // tiny batch: not worth a probe
+  if (p->batch_bytes < (256u << 10)) return RX_OK;  // tiny batch: not worth a probe
   // one run of the pack kernel with `lanes` streams per wavefront over the corner of the batch: the statistics
   // build (counters) or, with stats = false, the build that would really run (only the hand-off count is read)
   // the sample: up to 4 KB of each stream (how many states are active grows along a stream: the first KB of 4 KB windows
@@ -785,7 +924,12 @@ static int auto_probe_pack(rx_plan* p) {
     *spilled = (double)cnt[3] / (double)sample_streams;
     return RX_OK;
   };
-  const double units = (double)sample_streams * (double)std::max<size_t>(sample_len, 1);
+  double units = (double)sample_streams * (double)std::max<size_t>(sample_len, 1);
+  if (p->ragged) {  // the bytes of the sample sample_launch takes
+    units = 0;
+    for (size_t i = 0; i < sample_streams; i++) units += (double)std::min<size_t>(p->slots[i * p->n_streams / sample_streams].len, sample_len);
+    units = std::max(units, 1.0);
+  }
   double spilled = 0;
   int rc = run(16, true, false, false, &spilled);
   if (rc) return rc;
@@ -891,7 +1035,7 @@ static int auto_probe(rx_plan* p, bool reg_eligible) {
   if (rc || !reg_eligible) return rc;
   const RxHostNfa& h = p->nfa->h;
   rx_plan::AutoChoice& ch = p->choice;
-  if (p->n_streams * p->stream_len < (256u << 10)) {
+  if (p->batch_bytes < (256u << 10)) {
     rx_nfa* n = const_cast<rx_nfa*>(p->nfa);
     {
       std::lock_guard<std::mutex> lk(n->mu);
@@ -957,6 +1101,7 @@ static int batch_params(rx_plan* p) {
   a.anymatch = p->want_am ? p->d_am.p : nullptr;
   a.anymatch_stride = (uint32_t)p->am_stride;
   a.final_active = p->want_final ? p->d_final.p : nullptr;
+  a.slots = p->ragged ? p->d_slots.p : nullptr;
   // the testbench's clock count needs both streams of a pair in one wavefront: pack kernel only
   const bool pair = p->opts.collect_stats == 2;
   if (pair && ((p->opts.kernel != RX_KERNEL_AUTO && p->opts.kernel != RX_KERNEL_SYM_PACK) || (p->n_streams & 1) || p->have_init))
@@ -1073,6 +1218,17 @@ static int resolve_cfg(rx_plan* p, uint32_t kernel) {
   c.prune = p->tab.symidx_p != nullptr && !(o.flags & RX_OPT_NO_PRUNE) &&
             ((o.flags & RX_OPT_FORCE_PRUNE) != 0 ||
              (o.kernel == RX_KERNEL_SYM_PACK ? ch.probe_prune : by_auto && ch.prune));
+  if (p->ragged && c.kernel == RX_KERNEL_SYM_PACK && !c.fold) {
+    // the pack kernel's ragged form (plain, statistics, PRUNE builds) at the streams per wavefront it is instantiated for
+    // (the nearest one; ties to the larger; the FOLD builds' S are mapped above)
+    static const uint32_t ragged_s[] = {4, 8, 11, 13, 16, 22, 24, 32};
+    uint32_t pick = 16, best = ~0u;
+    for (uint32_t s : ragged_s) {
+      const uint32_t d = s > c.group_lanes ? s - c.group_lanes : c.group_lanes - s;
+      if (d <= best) { best = d; pick = s; }
+    }
+    c.group_lanes = pick;
+  }
   return RX_OK;
 }
 
@@ -1130,6 +1286,8 @@ extern "C" int rx_plan_launch(rx_plan* p) {
   a.zero_next = p->d_cset[p->cur_set ^ 1].p;
   a.zero_words = (uint32_t)set_words;
   if (p->want_mc) HIPCHK(hipMemsetAsync(p->d_mc.p, 0, p->n_streams * h.size * sizeof(uint32_t), p->stream));
+  // ragged batch: the kernels write a stream's any-match words up to its own last pass; the rest of the row reads 0
+  if (p->ragged && p->want_am) HIPCHK(hipMemsetAsync(p->d_am.p, 0, p->n_streams * p->am_stride * sizeof(uint32_t), p->stream));
   if (p->n_timed >= 4096) p->n_timed = 0;  // nobody is reading the times: recycle the pool
   if (p->n_timed == p->evs.size()) {
     std::pair<HipEvent, HipEvent> ev;
@@ -1288,6 +1446,8 @@ static void stats_traffic(const rx_plan* p, rx_stats& st, unsigned long long spi
   // + 1 bit per pass (per stream, rounded up to bytes) + 12 B per accept event
   st.alg_bytes = (uint64_t)p->params.n_consume * p->n_streams + 8 * st.sum_active + 4 * st.sum_edges +
                  (uint64_t)p->n_streams * ((st.n_passes + 7) / 8) + 12 * st.n_events;
+  if (p->ragged)  // the same sum stream by stream
+    st.alg_bytes = p->ragged_consume + 8 * st.sum_active + 4 * st.sum_edges + p->ragged_am_bytes + 12 * st.n_events;
   // per pair 1 reset clock + per pass [size + sum over states active in either stream of
   // (cost - 1)].  Only defined if no stream left the pack kernel.
   if (p->params.pair_cycles && spilled == 0)
@@ -1719,6 +1879,50 @@ extern "C" int rx_match(const rx_nfa* nfa, const uint8_t* bytes, size_t n_stream
   (void)hipEventRecord(t0, p->stream);
   if ((rc = rx_plan_upload(p, bytes, n_streams, stream_len, stride))) return done2(rc);
   if ((rc = rx_plan_set_init_active(p, init_active))) return done2(rc);
+  (void)hipEventRecord(t1, p->stream);
+  if ((rc = rx_plan_launch(p))) return done2(rc);
+  if ((rc = rx_plan_sync(p, nullptr))) return done2(rc);
+  const auto w0 = std::chrono::steady_clock::now();
+  if ((rc = rx_plan_download(p, res))) return done2(rc);  // honours res->struct_size
+  const auto w1 = std::chrono::steady_clock::now();
+  float h2d = 0;
+  (void)hipEventElapsedTime(&h2d, t0, t1);
+  res->stats.h2d_ms = h2d;
+  res->stats.d2h_ms = std::chrono::duration<double, std::milli>(w1 - w0).count();
+  return done2(RX_OK);
+  RX_CATCH
+}
+
+extern "C" int rx_match_ragged(const rx_nfa* nfa, const uint8_t* bytes, const uint64_t* offsets, size_t n_streams,
+                               const uint64_t* init_active, const rx_opts* opts, rx_result* res) {
+  RX_TRY
+  // everything that can be refused is refused before the device is touched
+  size_t longest = 0;
+  if (!nfa || !res || !ragged_offsets_ok(offsets, n_streams, ~(size_t)0, &longest)) return RX_EINVAL;
+  if (!bytes && offsets[n_streams] != offsets[0]) return RX_EINVAL;
+  const rx_opts o = read_opts(opts);
+  if (!ragged_opts_ok(o) || o.k_base + passes_for(longest, RX_MODE_FULL) > (1ull << 32)) return RX_EINVAL;
+  const bool has_compact = result_bytes(res) >= offsetof(rx_result, final_states_overflow) + sizeof(uint32_t);
+  if (has_compact && (res->final_states || res->final_off || res->final_cnt)) return RX_EINVAL;
+  if (res->anymatch && res->anymatch_stride < (size_t)((passes_for(longest, o.mode) + 31) / 32)) return RX_EINVAL;
+  rx_plan* p = nullptr;
+  int rc = rx_plan_create(nfa, opts, n_streams, longest, res->events ? res->events_cap : 0,
+                          res->match_count != nullptr, res->anymatch != nullptr, res->final_active != nullptr, &p);
+  if (rc) return rc;
+  auto done = [&](int code) {
+    rx_plan_free(p);
+    return code;
+  };
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  auto done2 = [&](int code) {
+    if (t0) (void)hipEventDestroy(t0);
+    if (t1) (void)hipEventDestroy(t1);
+    return done(code);
+  };
+  if (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess) return done2(RX_EHIP);
+  (void)hipEventRecord(t0, p->stream);
+  if ((rc = rx_plan_upload_ragged(p, bytes, offsets, n_streams))) return done2(rc);
+  if (init_active && (rc = rx_plan_set_init_active(p, init_active))) return done2(rc);
   (void)hipEventRecord(t1, p->stream);
   if ((rc = rx_plan_launch(p))) return done2(rc);
   if ((rc = rx_plan_sync(p, nullptr))) return done2(rc);

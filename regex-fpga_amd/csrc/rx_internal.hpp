@@ -42,6 +42,16 @@ static constexpr uint32_t RX_LIST_CAP = 128;  // sparse active-list capacity per
 static constexpr uint32_t RX_LIST_CAP_MAX = 512;  // ... and at most (rx_pick_launch: what four wavefronts per block leave room for)
 static constexpr uint32_t RX_SMALL_DEG = 8;   // CSR kernel: rows up to this length are scanned per lane
 
+// Ragged batch (rx_match_ragged, rx_plan_upload_ragged): one descriptor per wavefront SLOT.  The plan orders the slots by
+// length, longest first, so that the streams that share a pack wavefront end close together; every output row is indexed by
+// `id`, the stream's place in the caller's batch.  A stream's pass counts follow from `len` and the mode (RxParams::n_passes
+// != n_consume: RX_MODE_FULL).
+struct RxSlot {
+  uint64_t off;  // first byte of the stream, from RxParams::bytes
+  uint32_t len;
+  uint32_t id;
+};
+
 // Kernel argument block (passed by value).
 struct RxParams {
   // automaton in HBM — `words` is the .coe content unchanged: row_ptr = words, col = words+size+1
@@ -135,6 +145,9 @@ struct RxParams {
   uint32_t* dfa_hdr;                // [0] unused [1] next free chunk [2] states created [3] transitions built
   uint32_t dfa_pool_chunks;
   uint32_t dfa_hash_mask;
+  // ragged batch: [n_streams] descriptors (RxSlot), null for a uniform batch.  n_passes / n_consume are then those of the
+  // longest stream, stream_len its length; `stride` is unused.  Hand-off records (spill_streams) hold the SLOT index.
+  const RxSlot* slots;
 };
 
 static constexpr uint32_t RX_GROUP_CAP = 24;     // group kernel: active-list capacity per stream

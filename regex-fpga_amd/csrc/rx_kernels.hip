@@ -120,6 +120,79 @@ struct ByteFeed {
   }
 };
 
+// ---- ragged batches (RxParams::slots) ---------------------------------------------------------------
+// Bytes [off, off + 4) of a stream at any alignment: the aligned dword that holds byte `off`, the next one only if it still
+// holds bytes of the stream, then v_alignbyte; bytes at or beyond `len` read as 0.
+__device__ __forceinline__ uint32_t ragged_dword(const uint8_t* base, uint32_t len, uint32_t off) {
+  if (off >= len) return 0u;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(base) + off;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+  const uint32_t sh = (uint32_t)a & 3u, rem = len - off;
+  const uint32_t lo = w[0];
+  const uint32_t hi = (sh != 0u && rem > 4u - sh) ? w[1] : 0u;
+  const uint32_t v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+  return rem >= 4u ? v : v & ((1u << (8u * rem)) - 1u);
+}
+// Bytes [off, off + 16) of a stream at any alignment: the aligned 16-byte granule that holds byte `off`, the next one only if
+// it still holds bytes of the stream (no granule without any of the stream's bytes is read), then funnel shifts.
+__device__ __forceinline__ void ragged_granule(const uint8_t* base, uint32_t len, uint32_t off, uint32_t (&v)[4]) {
+  v[0] = v[1] = v[2] = v[3] = 0u;
+  if (off >= len) return;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(base) + off;
+  const uint4* g = reinterpret_cast<const uint4*>(a & ~(uintptr_t)15);
+  const uint32_t sh = (uint32_t)a & 15u, rem = len - off;
+  const uint4 q0 = g[0];
+  const uint4 q1 = (sh != 0u && rem > 16u - sh) ? g[1] : make_uint4(0u, 0u, 0u, 0u);
+  const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+  const uint32_t s4 = sh >> 2;
+  uint32_t x[5];
+#pragma unroll
+  for (uint32_t i = 0; i < 5u; i++) x[i] = s4 == 0u ? w[i] : (s4 == 1u ? w[i + 1u] : (s4 == 2u ? w[i + 2u] : w[i + 3u]));
+#pragma unroll
+  for (uint32_t i = 0; i < 4u; i++) {
+    const uint32_t t = __builtin_amdgcn_alignbyte(x[i + 1u], x[i], sh & 3u);
+    const uint32_t have = rem > 4u * i ? rem - 4u * i : 0u;
+    v[i] = have >= 4u ? t : t & ((1u << (8u * have)) - 1u);
+  }
+}
+// ByteFeed's interface over one ragged stream
+struct RaggedFeed {
+  const uint8_t* base;
+  uint32_t len;
+  __device__ __forceinline__ uint32_t load_chunk(uint32_t chunk, uint32_t lane) const {
+    return ragged_dword(base, len, chunk * 256u + lane * 4u);
+  }
+};
+// pass counts of a ragged stream of `len` bytes (RX_MODE_FULL: len + 1 passes, len consume a byte; tb-compat: len - 1 each)
+__device__ __forceinline__ void ragged_passes(const RxParams& p, uint32_t len, uint32_t& n_passes, uint32_t& n_consume) {
+  const bool full = p.n_passes != p.n_consume;
+  n_consume = full ? len : (len ? len - 1u : 0u);
+  n_passes = full ? len + 1u : n_consume;
+}
+// One stream of a wavefront-per-stream kernel: where its bytes are, its pass counts and the row its outputs go to.  `idx`
+// is the stream (uniform batch) or the slot (ragged batch: the RAGGED instantiations).
+template <bool RAGGED>
+struct StreamView {
+  uint32_t id, n_passes, n_consume;
+  std::conditional_t<RAGGED, RaggedFeed, ByteFeed> feed;
+  __device__ __forceinline__ StreamView(const RxParams& p, uint32_t idx) {
+    if constexpr (RAGGED) {
+      const RxSlot d = p.slots[idx];
+      id = d.id;
+      feed.base = p.bytes + d.off;
+      feed.len = d.len;
+      ragged_passes(p, d.len, n_passes, n_consume);
+    } else {
+      id = idx;
+      n_passes = p.n_passes;
+      n_consume = p.n_consume;
+      feed.base = p.bytes + (size_t)idx * p.stride;
+      feed.len = p.stream_len;
+      feed.aligned = ((reinterpret_cast<uintptr_t>(feed.base)) & 3u) == 0;
+    }
+  }
+};
+
 // ---- accept pulses (FPGA.v:210-226 -> testbench_BLK_Mem.sv:61-69) -----------------------------
 __device__ __forceinline__ void emit_events(const RxParams& p, bool acc, uint32_t state, uint32_t stream,
                                             uint32_t k, uint32_t lane, uint32_t& am_word) {
@@ -305,7 +378,7 @@ __device__ __forceinline__ void for_each_active(const RxParams& p, const StreamS
 // =================================================================================================
 // Kernel 1: wavefront-per-stream over the state-major CSR exactly as loaded
 // =================================================================================================
-template <bool STATS>
+template <bool STATS, bool RAGGED>
 __global__ void __launch_bounds__(256) rx_csr_wave_kernel(const RxParams p) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -316,18 +389,17 @@ __global__ void __launch_bounds__(256) rx_csr_wave_kernel(const RxParams p) {
   unsigned long long st_active = 0, st_edges = 0;
   zero_next_counters(p);
 
-  for (uint32_t stream = blockIdx.x * wpb + wib; stream < p.n_streams; stream += gridDim.x * wpb) {
+  for (uint32_t idx = blockIdx.x * wpb + wib; idx < p.n_streams; idx += gridDim.x * wpb) {
+    const StreamView<RAGGED> sv(p, idx);
+    const uint32_t stream = sv.id;
     StreamState st;
     stream_reset(p, st, my, p.init_active ? p.init_active + (size_t)stream * p.nw64x2 : nullptr, lane);
-    ByteFeed feed;
-    feed.base = p.bytes + (size_t)stream * p.stride;
-    feed.len = p.stream_len;
-    feed.aligned = ((reinterpret_cast<uintptr_t>(feed.base)) & 3u) == 0;
+    const auto& feed = sv.feed;
     uint32_t cur_word = 0, nxt_word = feed.load_chunk(0, lane);
     uint32_t am_word = 0;
 
-    for (uint32_t k = 0; k < p.n_passes; k++) {
-      const bool consume = k < p.n_consume;
+    for (uint32_t k = 0; k < sv.n_passes; k++) {
+      const bool consume = k < sv.n_consume;
       uint32_t c = 0;
       if (consume) {
         if ((k & 255u) == 0) {
@@ -380,7 +452,7 @@ __global__ void __launch_bounds__(256) rx_csr_wave_kernel(const RxParams p) {
         }
       });
       if (consume) stream_swap(p, st, lane);
-      if (p.anymatch && ((k & 31u) == 31u || k + 1 == p.n_passes)) {
+      if (p.anymatch && ((k & 31u) == 31u || k + 1 == sv.n_passes)) {
         if (lane == 0) p.anymatch[(size_t)stream * p.anymatch_stride + (k >> 5)] = am_word;
         am_word = 0;
       }
@@ -407,6 +479,7 @@ __global__ void __launch_bounds__(256) rx_csr_wave_kernel(const RxParams p) {
 // wavefront per stream fills the chip better.  Wave-uniform / block-uniform control flow throughout.
 static constexpr uint32_t RX_BLOCK_RESUME_MAX = 4096;
 
+template <bool RAGGED>
 __device__ __forceinline__ void resume_streams_by_block(const RxParams& p, uint32_t* lds, uint32_t total) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wib = tid >> 6, nthr = blockDim.x, nwav = blockDim.x >> 6;
   const uint32_t cap = (p.lds_words_per_stream - 2u * p.nw32) >> 1;
@@ -418,7 +491,8 @@ __device__ __forceinline__ void resume_streams_by_block(const RxParams& p, uint3
   const uint32_t* __restrict__ symidx = p.symidx;
   const uint32_t* __restrict__ ovf = p.ovf;
   for (uint32_t idx = blockIdx.x; idx < total; idx += gridDim.x) {  // (block-uniform)
-    const uint32_t stream = p.spill_streams[idx], k0 = p.spill_k[idx];
+    const StreamView<RAGGED> sv(p, p.spill_streams[idx]);
+    const uint32_t stream = sv.id, k0 = p.spill_k[idx];
     const uint32_t* row = p.spill_rows + (size_t)idx * p.nw64x2;
     __syncthreads();  // the previous stream's final set has been stored
     for (uint32_t w = tid; w < p.nw32; w += nthr) { cb[w] = row[w]; nb[w] = 0u; }
@@ -430,15 +504,12 @@ __device__ __forceinline__ void resume_streams_by_block(const RxParams& p, uint3
     }
     bool dense = true;  // S_k arrives as a bitmask row
     uint32_t n_cur = 0;
-    ByteFeed feed;
-    feed.base = p.bytes + (size_t)stream * p.stride;
-    feed.len = p.stream_len;
-    feed.aligned = ((reinterpret_cast<uintptr_t>(feed.base)) & 3u) == 0;
+    const auto& feed = sv.feed;
     uint32_t cur_word = 0, nxt_word = feed.load_chunk(k0 >> 8, lane);  // (every wavefront keeps its own copy of the bytes)
     __syncthreads();
 
-    for (uint32_t k = k0; k < p.n_passes; k++) {
-      const bool consume = k < p.n_consume;
+    for (uint32_t k = k0; k < sv.n_passes; k++) {
+      const bool consume = k < sv.n_consume;
       const bool pulses = k != k0;
       uint32_t* cnt = &ctrl[k & 1u];
       uint32_t c = 0;
@@ -532,7 +603,7 @@ __device__ __forceinline__ void resume_streams_by_block(const RxParams& p, uint3
       }
       if (tid == 0) {
         ctrl[(k + 1u) & 1u] = 0u;  // (nobody touches the other counter before the barrier below)
-        if (p.anymatch && ((k & 31u) == 31u || k + 1 == p.n_passes)) {
+        if (p.anymatch && ((k & 31u) == 31u || k + 1 == sv.n_passes)) {
           p.anymatch[(size_t)stream * p.anymatch_stride + (k >> 5)] = ctrl[2];
           ctrl[2] = 0u;
         }
@@ -548,7 +619,7 @@ __device__ __forceinline__ void resume_streams_by_block(const RxParams& p, uint3
   }
 }
 
-template <bool STATS>
+template <bool STATS, bool RAGGED>
 __global__ void __launch_bounds__(256) rx_sym_wave_kernel(const RxParams p) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -565,31 +636,33 @@ __global__ void __launch_bounds__(256) rx_sym_wave_kernel(const RxParams p) {
     const unsigned long long n = *p.spill_count;
     total = n < p.n_streams ? (uint32_t)n : p.n_streams;
     if (!STATS && wpb >= 2u && total <= RX_BLOCK_RESUME_MAX) {  // few hand-offs: the whole block on one stream at a time
-      resume_streams_by_block(p, lds, total);
+      resume_streams_by_block<RAGGED>(p, lds, total);
       return;
     }
   }
 
   for (uint32_t idx = blockIdx.x * wpb + wib; idx < total; idx += gridDim.x * wpb) {
-    uint32_t stream = idx, k0 = 0;
+    uint32_t sidx = idx, k0 = 0;  // sidx: the stream (uniform batch) or its slot (ragged batch)
     const uint32_t* init_row = p.init_active ? p.init_active + (size_t)idx * p.nw64x2 : nullptr;
+    if constexpr (RAGGED) {
+      if (init_row) init_row = p.init_active + (size_t)p.slots[idx].id * p.nw64x2;
+    }
     if (p.resume) {
-      stream = p.spill_streams[idx];
+      sidx = p.spill_streams[idx];
       k0 = p.spill_k[idx];
       init_row = p.spill_rows + (size_t)idx * p.nw64x2;
     }
     StreamState st;
     stream_reset(p, st, my, init_row, lane);
-    ByteFeed feed;
-    feed.base = p.bytes + (size_t)stream * p.stride;
-    feed.len = p.stream_len;
-    feed.aligned = ((reinterpret_cast<uintptr_t>(feed.base)) & 3u) == 0;
+    const StreamView<RAGGED> sv(p, sidx);
+    const uint32_t stream = sv.id;
+    const auto& feed = sv.feed;
     uint32_t cur_word = 0, nxt_word = feed.load_chunk(k0 >> 8, lane);
     // the hand-off pass already emitted its accept pulses; keep the bits of its partial bitmap word
     uint32_t am_word = (p.resume && p.anymatch) ? p.anymatch[(size_t)stream * p.anymatch_stride + (k0 >> 5)] : 0u;
 
-    for (uint32_t k = k0; k < p.n_passes; k++) {
-      const bool consume = k < p.n_consume;
+    for (uint32_t k = k0; k < sv.n_passes; k++) {
+      const bool consume = k < sv.n_consume;
       const bool pulses = !(p.resume && k == k0);
       uint32_t c = 0;
       if (consume) {
@@ -627,7 +700,7 @@ __global__ void __launch_bounds__(256) rx_sym_wave_kernel(const RxParams p) {
         }
       });
       if (consume) stream_swap(p, st, lane);
-      if (p.anymatch && ((k & 31u) == 31u || k + 1 == p.n_passes)) {
+      if (p.anymatch && ((k & 31u) == 31u || k + 1 == sv.n_passes)) {
         if (lane == 0) p.anymatch[(size_t)stream * p.anymatch_stride + (k >> 5)] = am_word;
         am_word = 0;
       }
@@ -1029,9 +1102,18 @@ struct PackLayout {
 // from pass 1 on, and what its row emits on the current byte comes from a (class x next class) table in LDS, looked
 // up by the stream's OWNER lane while the list entries' slice gather is in flight; of its targets only those that are
 // accept states or survive the next byte are inserted.  Six-bit stream slots (up to 64 streams per wavefront).
-template <int S, bool STATS, bool PROF, bool PRUNE, bool FOLD>
+// RAGGED: the batch is ragged (RxParams::slots).  Slot j of wavefront w takes descriptor w*S + j; the wavefront runs to the
+// longest of its streams, and a stream that reaches its own end RETIRES before the pass that would consume its next byte
+// (`retire`: RX_MODE_FULL's accept-only last pass, its final set stored from the list entries, its entries out of the list,
+// its slot idle) — the hand-off's eviction without the hand-off.  Windows come through aligned 16-byte loads and funnel
+// shifts (ragged_granule).  Every look-ahead decision (PRUNE's and FOLD's "is there a next byte") is taken against the
+// entry's own stream end; FOLD: a retired slot's owner lane no longer looks up the folded state's emissions, its passes set
+// no `busy` bits, the idle-pass skip never steps over a retirement, and a stream that consumed no byte never holds the
+// folded state.  Not in the stamped (PROF) build.
+template <int S, bool STATS, bool PROF, bool PRUNE, bool FOLD, bool RAGGED>
 __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxParams p) {
   static_assert(!((PRUNE || FOLD) && (STATS || PROF)), "statistics / stamped builds run unpruned and unfolded");
+  static_assert(!(RAGGED && PROF), "ragged batches: not in the stamped build");
   constexpr bool LOOK = PRUNE || FOLD;  // the window carries one byte of look-ahead
   constexpr uint32_t MARK = 1u << 29;  // STATS only: entry was inserted from a multi-target row
   unsigned long long t_prev = 0, t_sum[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -1093,9 +1175,45 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
   // input windows: lane = 4*slot + part fetches bytes [64*chunk + 16*part, +16) of stream `slot`
   static_assert(S >= 1 && S <= (FOLD ? 64 : 32), "five-bit (FOLD: six-bit) stream slot; the window loader covers 16 streams per wave-load");
   constexpr uint32_t NLOAD = (S + 15) / 16;  // wave-loads per refill
+  // RAGGED: the owner lane's stream (output row, pass counts), the loader's streams, and the passes at which the next stream
+  // retires / the wavefront ends (wave-uniform)
+  uint32_t my_id = stream0 + lane, my_nc = 0u, my_np = 0u, next_ret = ~0u, wave_nc = 0u;
+  const uint8_t* ld_base[NLOAD];
+  uint32_t ld_len[NLOAD], ld_nc[NLOAD];  // (ld_nc: the loader slot's n_consume, for FOLD's `busy` bits)
+  if constexpr (RAGGED) {
+    if (lane < n_mine) {
+      const RxSlot d = p.slots[stream0 + lane];
+      my_id = d.id;
+      ragged_passes(p, d.len, my_np, my_nc);
+    }
+#pragma unroll
+    for (uint32_t g = 0; g < NLOAD; g++) {
+      const uint32_t slot = g * 16u + (lane >> 2);
+      const RxSlot d = p.slots[stream0 + (slot < n_mine ? slot : 0u)];
+      ld_base[g] = p.bytes + d.off;
+      ld_len[g] = slot < n_mine ? d.len : 0u;
+      uint32_t np_g;
+      ragged_passes(p, ld_len[g], np_g, ld_nc[g]);
+    }
+    uint32_t mx = lane < n_mine ? my_nc : 0u, mn = lane < n_mine ? my_nc : ~0u;
+    for (int d = 32; d >= 1; d >>= 1) {
+      const uint32_t a = (uint32_t)__shfl_xor((int)mx, d), b = (uint32_t)__shfl_xor((int)mn, d);
+      mx = a > mx ? a : mx;
+      mn = b < mn ? b : mn;
+    }
+    wave_nc = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
+    next_ret = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
+  }
   auto load_win = [&](uint32_t chunk, uint32_t (&o)[NLOAD][4]) {
 #pragma unroll
     for (uint32_t g = 0; g < NLOAD; g++) {
+      if constexpr (RAGGED) {
+        uint32_t v[4];
+        ragged_granule(ld_base[g], ld_len[g], chunk * 64u + (lane & 3u) * 16u, v);
+#pragma unroll
+        for (int w4 = 0; w4 < 4; w4++) o[g][w4] = v[w4];
+        continue;
+      }
       const uint32_t slot = g * 16u + (lane >> 2), part = lane & 3u;
       const bool have = slot < n_mine;
       const uint8_t* bp = p.bytes + (size_t)(stream0 + (have ? slot : 0)) * p.stride;
@@ -1176,8 +1294,9 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
           const uint32_t c0 = (uint32_t)((i < 8u ? lo : hi) >> (8u * (i & 7u))) & 0xFFu;
           const uint32_t c1 = i == 15u ? nf : (uint32_t)((i + 1u < 8u ? lo : hi) >> (8u * ((i + 1u) & 7u))) & 0xFFu;
           const uint32_t kg = k + part * 16u + i;
-          const bool last = kg + 1u >= p.n_consume;
-          const bool known = kg >= 1u && kg < p.n_consume && (last || !(part == 3u && i == 15u));
+          const uint32_t nc_g = RAGGED ? ld_nc[g] : p.n_consume;  // (a retired slot: nc_g <= k, nothing is known)
+          const bool last = kg + 1u >= nc_g;
+          const bool known = kg >= 1u && kg < nc_g && (last || !(part == 3u && i == 15u));
           const uint32_t em = known ? pintab[c0 * p.pin_cols + (last ? ncls : c1)] : 0u;
           bits |= (em != 0u ? 1u : 0u) << i;
         }
@@ -1195,7 +1314,7 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
     wave_sync();
     if (owner) {
       uint32_t* am = sreg0 + lane * L::STRIDE + 2u * L::FW + L::WINW;
-      uint32_t* dst = p.anymatch + (size_t)(stream0 + lane) * p.anymatch_stride + 8u * group;
+      uint32_t* dst = p.anymatch + (size_t)(RAGGED ? my_id : stream0 + lane) * p.anymatch_stride + 8u * group;
       if ((p.anymatch_stride & 7u) == 0u) {
         reinterpret_cast<uint4*>(dst)[0] = make_uint4(am[0], am[1], am[2], am[3]);
         reinterpret_cast<uint4*>(dst)[1] = make_uint4(am[4], am[5], am[6], am[7]);
@@ -1284,7 +1403,7 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
     if (pin_now && owner) {
       const uint8_t* wb = reinterpret_cast<const uint8_t*>(sreg0 + lane * L::STRIDE + 2u * L::FW);
       const uint32_t c0 = wb[kk];
-      const uint32_t sel = (k + 1u < p.n_consume) ? (uint32_t)wb[kk + 1u] : ncls_v;  // byte 64 of the window: stash
+      const uint32_t sel = (k + 1u < (RAGGED ? my_nc : p.n_consume)) ? (uint32_t)wb[kk + 1u] : ncls_v;  // byte 64 of the window: stash
       vA = pintab[c0 * p.pin_cols + sel];
     }
     bool pin_done = !pin_now;
@@ -1327,7 +1446,7 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
         if (wballot(e & RXE_ACCEPT) != 0ull && !replay) {
           const bool acc = (e & RXE_ACCEPT) != 0u;
           uint32_t dummy = 0;
-          emit_events(p, acc, s, stream0 + sid, k, lane, dummy);
+          emit_events(p, acc, s, RAGGED ? (uint32_t)__shfl((int)my_id, (int)sid) : stream0 + sid, k, lane, dummy);
           if (acc) atomicOr(&sreg[2u * L::FW + L::WINW + ((k >> 5) & (L::AMW - 1u))], 1u << (k & 31u));
         }
       };
@@ -1339,6 +1458,10 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
       const uint32_t c = reinterpret_cast<const uint8_t*>(sreg + 2u * L::FW)[kk];  // class of that stream's input_char
       uint32_t cnx = 0u;  // PRUNE: class of its NEXT byte (byte 64 of the window: the stash)
       if (PRUNE) cnx = reinterpret_cast<const uint8_t*>(sreg + 2u * L::FW)[kk + 1u];
+      // RAGGED PRUNE: whether the entry's OWN stream consumes another byte (its last byte's sets are reported: no pruning)
+      bool more = true;
+      if (RAGGED && PRUNE) more = k + 1u < (uint32_t)__shfl((int)my_nc, (int)sid);
+      const uint32_t keep = RAGGED ? ((narrow && more) ? 0u : 0x00FF0000u) : keep_all;
       // zero the filter word this entry went through (lanes without an entry hit some word of the CURRENT filter of
       // a valid slot; that filter is being wiped this pass anyway and is not read before the next swap)
       if (!RX_AB_PREDICATE_IDLE || have) *fword(sreg, fcur_b, s & HMASK) = 0u;
@@ -1393,7 +1516,7 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
       // (PRUNE, narrow index: an inline target that is no accept state and has no edge on the stream's next byte can neither
       // pulse nor produce a successor: it is not inserted — except at the stream's last byte, whose sets are reported)
       bool inl = FOLD ? (x & (RXE_INLINE | RXE_PIN)) == RXE_INLINE : (x & RXE_INLINE) != 0u;
-      if (PRUNE) inl = inl && (((x | keep_all) >> (16u + (cnx & 7u))) & 1u) != 0u;
+      if (PRUNE) inl = inl && (((x | keep) >> (16u + (cnx & 7u))) & 1u) != 0u;
       const uint32_t v1 = (!PRUNE && !FOLD) ? (x >> 31) << (h1 & 31u) : (inl ? 1u << (h1 & 31u) : 0u);
       uint32_t o0 = 0u, o1 = 0u;
       if (!RX_AB_PREDICATE_IDLE || v0) o0 = atomicOr(fword(sreg, fnext_b, h0), v0);
@@ -1438,7 +1561,7 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
           // it from the kernel-argument segment, an s_load and its wait in every pass of every workload with multi-target rows:
           // SQ_INSTS_SMEM 1e5 -> 5.9e6 per launch on the rule-set stand-in; taking it out did not move that launch's time, though)
           uint32_t sel = ncls_v;
-          if (k + 1u < p.n_consume) sel = reinterpret_cast<const uint8_t*>(sreg + 2u * L::FW)[kk + 1u];  // byte 64: stash
+          if (RAGGED ? more : k + 1u < p.n_consume) sel = reinterpret_cast<const uint8_t*>(sreg + 2u * L::FW)[kk + 1u];  // byte 64: stash
           const uint32_t d = (x & RXE_OVF) ? p.ovf_dir[(x & xtmask) * (ncls_v + 1u) + sel] : 0u;
           myoff = d >> 8;
           mycnt = d & 255u;
@@ -1548,7 +1671,7 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
       cq->spill_k[my_slot] = k;
       if (cq->anymatch) {  // the words of the current 256-pass group up to the one of pass k (which the wave kernel reads back)
         const uint32_t* am = sreg0 + lane * L::STRIDE + 2u * L::FW + L::WINW;
-        uint32_t* dst = cq->anymatch + (size_t)(stream0 + lane) * cq->anymatch_stride + ((k >> 8) << 3);
+        uint32_t* dst = cq->anymatch + (size_t)(RAGGED ? my_id : stream0 + lane) * cq->anymatch_stride + ((k >> 8) << 3);
         for (uint32_t w = 0; w <= ((k >> 5) & (L::AMW - 1u)); w++) dst[w] = am[w];
       }
     }
@@ -1584,11 +1707,94 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
     wave_sync();
   };
 
+  // RAGGED: the streams whose last consumed byte was byte k - 1 leave before pass k (wave-uniform, outside the pass):
+  // RX_MODE_FULL's last pass of theirs (accept pulses only), their any-match words up to their own last pass, their final
+  // sets straight from the list entries (the next-list buffer is dead between passes and serves as scratch), their entries
+  // out of the list.  Then the pass at which the next stream retires.
+  auto retire = [&](const uint32_t k) {
+    const unsigned long long rm = wballot(owner && my_nc == k);  // (owner: slot still here)
+    wave_sync();
+    if (rm != 0ull) {
+      if (p.n_passes != p.n_consume) {  // RX_MODE_FULL
+        for (uint32_t b0 = 0; b0 < N; b0 += 64u) {
+          const uint32_t li = b0 + lane;
+          const uint32_t e = li < N ? clist[li] : 0u;
+          const uint32_t es = (e >> SID_SHIFT) & SID_BITS;
+          const bool acc = li < N && ((rm >> es) & 1ull) != 0ull && (e & RXE_ACCEPT) != 0u;
+          const uint32_t id = (uint32_t)__shfl((int)my_id, (int)es);
+          if (wballot(acc) != 0ull) {
+            uint32_t dummy = 0;
+            emit_events(p, acc, e & RXE_TGT_MASK, id, k, lane, dummy);
+            if (acc) atomicOr(&sreg0[es * L::STRIDE + 2u * L::FW + L::WINW + ((k >> 5) & (L::AMW - 1u))], 1u << (k & 31u));
+          }
+        }
+        wave_sync();
+      }
+      if (p.anymatch && ((rm >> lane) & 1ull) != 0ull && my_np > 256u * (k >> 8)) {
+        // the words of the current 256-pass group up to the stream's last pass (whole groups before it are out already)
+        const uint32_t* am = sreg0 + lane * L::STRIDE + 2u * L::FW + L::WINW;
+        uint32_t* dst = p.anymatch + (size_t)my_id * p.anymatch_stride;
+        for (uint32_t w = 8u * (k >> 8); w <= ((my_np - 1u) >> 5); w++) dst[w] = am[w & (L::AMW - 1u)];
+      }
+      if (p.final_active) {
+        constexpr uint32_t SLICE = L::LISTW & ~1u;
+        unsigned long long mm = rm;
+        while (mm) {
+          const uint32_t sl = (uint32_t)__builtin_ctzll(mm);
+          mm &= mm - 1ull;
+          uint2* row8 = reinterpret_cast<uint2*>(p.final_active + (size_t)bcast(my_id, sl) * p.nw64x2);
+          for (uint32_t w0 = 0; w0 < p.nw64x2; w0 += SLICE) {
+            const uint32_t nwords = p.nw64x2 - w0 < SLICE ? p.nw64x2 - w0 : SLICE;
+            wave_sync();
+            for (uint32_t w = lane; w < nwords; w += 64u) nlist[w] = 0u;
+            wave_sync();
+            for (uint32_t li = lane; li < N; li += 64u) {
+              const uint32_t e = clist[li];
+              const uint32_t wd = (e & RXE_TGT_MASK) >> 5;
+              if (((e >> SID_SHIFT) & SID_BITS) == sl && wd >= w0 && wd - w0 < nwords) atomicOr(&nlist[wd - w0], 1u << (e & 31u));
+            }
+            const uint32_t nc_sl = bcast(my_nc, sl);
+            if (FOLD && lane == 0 && nc_sl >= 1u) {  // the folded state, in every set after the stream's first byte
+              const uint32_t wd = p.pin_state >> 5;
+              if (wd >= w0 && wd - w0 < nwords) atomicOr(&nlist[wd - w0], 1u << (p.pin_state & 31u));
+            }
+            wave_sync();
+            for (uint32_t w = lane; w < nwords / 2u; w += 64u) row8[(w0 >> 1) + w] = make_uint2(nlist[2u * w], nlist[2u * w + 1u]);
+          }
+        }
+        wave_sync();
+      }
+      uint32_t M = 0;  // the list without them
+      for (uint32_t b0 = 0; b0 < N; b0 += 64u) {
+        const uint32_t li = b0 + lane;
+        const uint32_t e = li < N ? clist[li] : 0u;
+        const bool keep = li < N && ((rm >> ((e >> SID_SHIFT) & SID_BITS)) & 1ull) == 0ull;
+        const uint64_t mk = wballot(keep);
+        if (keep) nlist[rank_below_plus(mk, M)] = e;
+        M += (uint32_t)__popcll(mk);
+      }
+      {
+        uint32_t* t = clist; clist = nlist; nlist = t;
+      }
+      N = M;
+      alive &= ~rm;
+      owner = lane < n_mine && ((alive >> lane) & 1ull) != 0ull;
+      if (alive == 0ull) spilled = true;  // nothing left here
+    }
+    uint32_t mn = owner ? my_nc : ~0u;
+    for (int d = 32; d >= 1; d >>= 1) {
+      const uint32_t b = (uint32_t)__shfl_xor((int)mn, d);
+      mn = b < mn ? b : mn;
+    }
+    next_ret = (uint32_t)__builtin_amdgcn_readfirstlane((int)mn);
+    wave_sync();
+  };
+
   uint32_t k = 0;
-  const uint32_t n_consume = p.n_consume < p.n_passes ? p.n_consume : p.n_passes;
+  const uint32_t n_consume = RAGGED ? wave_nc : (p.n_consume < p.n_passes ? p.n_consume : p.n_passes);
   while (k < n_consume && !spilled) {  // k is a multiple of 64 here
     refill(k);
-    if (FOLD && k == 0u) {
+    if (FOLD && !RAGGED && k == 0u) {  // (RAGGED: `retire` stores whole rows)
       // FOLD builds serve inputs on which most streams end without a list entry: their final rows are all zero but for the
       // folded state's bit.  The rows are cleared HERE — behind the wait for the first window (on gfx9 stores count in
       // `vmcnt`: issued before it they would sit in front of the first bytes), in the shadow of the first passes — and at the
@@ -1606,13 +1812,19 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
     while (k < kend && !spilled) {
       const uint32_t k32 = kend - k < 32u ? kend : k + 32u;
       do {
+        if (RAGGED && k == next_ret) {
+          retire(k);
+          if (spilled) break;
+        }
         if (FOLD && __builtin_amdgcn_readfirstlane((int)N) == 0) {
           // nothing in the wave's list: the passes up to the next emission of a folded state change nothing at all
           // (both lists empty, both filters clean, no pulse) — skip them in one step
           const unsigned long long rest = busy >> (k & 63u);
           if ((rest & 1ull) == 0ull) {
             const uint32_t skip = rest ? (uint32_t)__builtin_ctzll(rest) : 64u;
-            k += skip < k32 - k ? skip : k32 - k;
+            uint32_t lim = k32 - k;
+            if (RAGGED && next_ret - k < lim) lim = next_ret - k;  // (next_ret > k here) never over a retirement
+            k += skip < lim ? skip : lim;
             continue;
           }
         }
@@ -1631,12 +1843,13 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
       if (LOOK && (k & 63u) == 32u) stash_next_first();
     }
   }
-  while (k < p.n_passes && !spilled) {  // RX_MODE_FULL: pass N
+  if (RAGGED && !spilled) retire(k);  // the wavefront's longest streams (k == their n_consume); everything is out after it
+  while (!RAGGED && k < p.n_passes && !spilled) {  // RX_MODE_FULL: pass N
     pass(k, std::false_type{}, std::false_type{});
     k++;
     if (p.anymatch && (k & 255u) == 0u) store_anymatch((k >> 8) - 1u);
   }
-  if (!spilled && p.anymatch && (k & 255u) != 0u) store_anymatch(k >> 8);
+  if (!RAGGED && !spilled && p.anymatch && (k & 255u) != 0u) store_anymatch(k >> 8);
   if (PROF && lane == 0) {
     for (int q = 0; q < 7; q++) atomicAdd(&p.counters[8 + q], t_sum[q]);
     // wave 0 only: [63:32] shader cycles / 64, [31:0] 100 MHz ticks, both over the whole wave
@@ -1647,7 +1860,7 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
   // buffer is dead now and serves as scratch.
   const bool pin_in = FOLD && n_consume >= 1u;  // the folded state is in every set after the first byte
   const RxColdParams cq = cold_params();
-  if (cq->fin_states && !spilled) {
+  if (!RAGGED && cq->fin_states && !spilled) {
     // As compact lists, straight from the list entries — no bitmask row is ever built.  Per entry its rank among its
     // stream's entries (ascending state), per stream (owner lane) the count and, FOLD, where the folded state goes; one
     // atomic per wavefront for the space.
@@ -1696,7 +1909,7 @@ __global__ void __launch_bounds__(FOLD ? 512 : 256) rx_sym_pack_kernel(const RxP
         if (o < cq->fin_cap) cq->fin_states[o] = sq;
       }
     }
-  } else if (cq->final_active && !spilled) {
+  } else if (!RAGGED && cq->final_active && !spilled) {
     // As bitmask rows: each row is built in LDS (in slices of the scratch buffer's size for automata whose row is longer)
     // and stored ONCE with 8-byte stores — no zeroing in the prologue, no global atomics.
     constexpr uint32_t SLICE = L::LISTW & ~1u;
@@ -2066,7 +2279,7 @@ __global__ void __launch_bounds__(256) rx_dfa_kernel(const RxParams p) {
 // quieter shipped trace: 63 % of all passes; uniform bytes: nearly all).  A build of its own because the test, three
 // instructions per group, costs the other build's code 4-14 % through register allocation (measured: hi trace 42.4 ->
 // 44.7 ms, l7 small batches 0.23 -> 0.26 ms): AUTO picks per batch (rx_api.cpp).
-template <bool FOLD, bool SKIP>
+template <bool FOLD, bool SKIP, bool RAGGED>
 __global__ void __launch_bounds__(64) rx_sym_reg_kernel(const RxParams p) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -2075,22 +2288,21 @@ __global__ void __launch_bounds__(64) rx_sym_reg_kernel(const RxParams p) {
   cmapw[lane] = p.byte_class[lane];
   wave_sync();
   zero_next_counters(p);
-  const uint32_t stream = blockIdx.x;
-  if (stream >= p.n_streams) return;
+  const uint32_t slot = blockIdx.x;  // the stream (uniform batch) or its slot (ragged batch)
+  if (slot >= p.n_streams) return;
+  const StreamView<RAGGED> sv(p, slot);
+  const uint32_t stream = sv.id;
   zero_final_rows(p, stream, 1u, lane);
   const uint32_t ncls = p.n_classes, ncls8 = ncls * 8u;
   const uint32_t FREE = p.size;  // the empty row behind the index
   const char* __restrict__ regidx = reinterpret_cast<const char*>(p.regidx);
   const uint32_t* __restrict__ ovf = p.ovf;
-  ByteFeed feed;
-  feed.base = p.bytes + (size_t)stream * p.stride;
-  feed.len = p.stream_len;
-  feed.aligned = ((reinterpret_cast<uintptr_t>(feed.base)) & 3u) == 0;
+  const auto& feed = sv.feed;
   auto classes = [&](uint32_t v) {
     return (uint32_t)cmap[v & 0xFFu] | ((uint32_t)cmap[(v >> 8) & 0xFFu] << 8) | ((uint32_t)cmap[(v >> 16) & 0xFFu] << 16) |
            ((uint32_t)cmap[v >> 24] << 24);
   };
-  const uint32_t n_consume = p.n_consume < p.n_passes ? p.n_consume : p.n_passes;
+  const uint32_t n_consume = sv.n_consume < sv.n_passes ? sv.n_consume : sv.n_passes;
   // byte classes: lane j holds the classes of bytes 4j..4j+3 of the current 256-byte chunk (cw) and of the next (cwn);
   // the raw chunk after that is in flight.  va[q]: what the folded state emits in pass (chunk base + 4j + q).
   uint32_t cw = 0, cwn = classes(feed.load_chunk(0, lane)), raw = feed.load_chunk(1, lane);
@@ -2159,12 +2371,12 @@ __global__ void __launch_bounds__(64) rx_sym_reg_kernel(const RxParams p) {
       // more than 64 active states: hand the stream (S_k, k) to the wave kernel
       unsigned long long b = 0;
       if (lane == 0) b = atomicAdd(p.spill_count, 1ull);
-      const uint32_t slot = bcast((uint32_t)b, 0);
-      uint32_t* row = p.spill_rows + (size_t)slot * p.nw64x2;
+      const uint32_t at = bcast((uint32_t)b, 0);
+      uint32_t* row = p.spill_rows + (size_t)at * p.nw64x2;
       for (uint32_t w = lane; w < p.nw64x2; w += 64u) row[w] = 0u;
       if (lane == 0) {
-        p.spill_streams[slot] = stream;
-        p.spill_k[slot] = k;
+        p.spill_streams[at] = slot;
+        p.spill_k[at] = k;
         if (p.anymatch) p.anymatch[(size_t)stream * p.anymatch_stride + (k >> 5)] = am_word;
       }
       __threadfence();
@@ -2284,14 +2496,14 @@ __global__ void __launch_bounds__(64) rx_sym_reg_kernel(const RxParams p) {
   }
   if (!handed_off) {
     bool unsaved = (k & 31u) != 0u;  // passes whose any-match bits are still in am_word
-    if (k < p.n_passes) {  // RX_MODE_FULL: pass N only looks for accept states
+    if (k < sv.n_passes) {  // RX_MODE_FULL: pass N only looks for accept states
       if (macc != 0ull) pulses(k);
       k++;
       unsaved = true;
     }
     if (p.anymatch && unsaved) store_anymatch(k - 1u);
   }
-  if (stream == 0 && lane == 0) {
+  if (slot == 0 && lane == 0) {
     p.counters[8] = __builtin_amdgcn_s_memtime() - t0c;
     p.counters[9] = __builtin_amdgcn_s_memrealtime() - t0r;
   }
@@ -2445,7 +2657,8 @@ static int launch_group(const RxParams& p, const RxLaunchCfg& cfg, hipStream_t s
                    : launch_one(rx_sym_group_kernel<G, false>, p, grid ? grid : 1, wpb * 64u, lds, s);
 }
 
-template <int S, bool PRUNE>
+// RAGGED: the ragged instantiations (plain, statistics and PRUNE builds; launch_ragged maps group_lanes to the S they exist for)
+template <int S, bool PRUNE, bool RAGGED>
 static int launch_pack_as(const RxParams& p, const RxLaunchCfg& cfg, hipStream_t s) {
   using L = PackLayout<S, PRUNE, false>;
   const uint32_t wpb = 4;
@@ -2453,22 +2666,22 @@ static int launch_pack_as(const RxParams& p, const RxLaunchCfg& cfg, hipStream_t
   const uint32_t grid = (waves + wpb - 1) / wpb;
   const uint32_t g = grid ? grid : 1;
   const uint32_t lds = (L::CMAPW + wpb * L::WAVE_WORDS) * 4u;
-  if (PRUNE) return launch_one(rx_sym_pack_kernel<S, false, false, true, false>, p, g, wpb * 64u, lds, s);
-  if (cfg.stats) return launch_one(rx_sym_pack_kernel<S, true, false, false, false>, p, g, wpb * 64u, lds, s);
-  if (S == 16 && cfg.profile_pack)  // stamped diagnostic build, see the kernel's PROF note
-    return launch_one(rx_sym_pack_kernel<16, false, true, false, false>, p, g, wpb * 64u, lds, s);
-  return launch_one(rx_sym_pack_kernel<S, false, false, false, false>, p, g, wpb * 64u, lds, s);
+  if (PRUNE) return launch_one(rx_sym_pack_kernel<S, false, false, true, false, RAGGED>, p, g, wpb * 64u, lds, s);
+  if (cfg.stats) return launch_one(rx_sym_pack_kernel<S, true, false, false, false, RAGGED>, p, g, wpb * 64u, lds, s);
+  if (!RAGGED && S == 16 && cfg.profile_pack)  // stamped diagnostic build, see the kernel's PROF note
+    return launch_one(rx_sym_pack_kernel<16, false, true, false, false, false>, p, g, wpb * 64u, lds, s);
+  return launch_one(rx_sym_pack_kernel<S, false, false, false, false, RAGGED>, p, g, wpb * 64u, lds, s);
 }
 
-template <int S>
+template <int S, bool RAGGED = false>
 static int launch_pack(const RxParams& p, const RxLaunchCfg& cfg, hipStream_t s) {
-  if (cfg.prune && !cfg.stats && p.symidx_p) return launch_pack_as<S, true>(p, cfg, s);
-  return launch_pack_as<S, false>(p, cfg, s);
+  if (cfg.prune && !cfg.stats && p.symidx_p) return launch_pack_as<S, true, RAGGED>(p, cfg, s);
+  return launch_pack_as<S, false, RAGGED>(p, cfg, s);
 }
 
 // FOLD builds: the block shares one copy of the folding table, so blocks are as large as the LDS allows (up to 8
 // wavefronts); never with statistics.
-template <int S>
+template <int S, bool RAGGED = false>
 static int launch_fold(const RxParams& p, const RxLaunchCfg& cfg, hipStream_t s, size_t lds_per_cu) {
   const bool prune = cfg.prune && p.symidx_p;
   const uint32_t ww = prune ? PackLayout<S, true, true>::WAVE_WORDS : PackLayout<S, false, true>::WAVE_WORDS;
@@ -2491,21 +2704,94 @@ static int launch_fold(const RxParams& p, const RxLaunchCfg& cfg, hipStream_t s,
   const uint32_t grid = (waves + wpb - 1) / wpb;
   const uint32_t g = grid ? grid : 1;
   const uint32_t lds = (fixed + wpb * ww) * 4u;
-  if (prune) return launch_one(rx_sym_pack_kernel<S, false, false, true, true>, p, g, wpb * 64u, lds, s);
-  return launch_one(rx_sym_pack_kernel<S, false, false, false, true>, p, g, wpb * 64u, lds, s);
+  if (prune) return launch_one(rx_sym_pack_kernel<S, false, false, true, true, RAGGED>, p, g, wpb * 64u, lds, s);
+  return launch_one(rx_sym_pack_kernel<S, false, false, false, true, RAGGED>, p, g, wpb * 64u, lds, s);
+}
+
+// second launch of a two-tier kernel: the wave kernel finishes whatever the first one handed off (usually nothing; the count
+// is read on the device, so no host round-trip)
+template <bool RAGGED>
+static int launch_resume(const RxParams& p, const RxLaunchCfg& cfg, hipStream_t s) {
+  RxParams r = p;
+  r.resume = 1;
+  r.zero_next = nullptr;  // the first launch of the pair has done it
+  r.zero_words = 0;
+  const uint32_t wpb = cfg.block_threads / 64u;
+  uint32_t grid = (p.n_streams + wpb - 1) / wpb;
+  const uint32_t fill = (cfg.cu_count > 0 ? (uint32_t)cfg.cu_count : 256u) * 8u;  // enough blocks to fill the chip
+  if (grid > fill) grid = fill;
+  return cfg.stats ? launch_one(rx_sym_wave_kernel<true, RAGGED>, r, grid ? grid : 1, cfg.block_threads, cfg.lds_bytes, s)
+                   : launch_one(rx_sym_wave_kernel<false, RAGGED>, r, grid ? grid : 1, cfg.block_threads, cfg.lds_bytes, s);
+}
+
+// Ragged batches (RxParams::slots): the RAGGED instantiations.  The plan refuses the group and DFA kernels, the pack
+// kernel's stamped build and the pair statistics, and maps group_lanes to 4/8/11/13/16/22/24/32 (FOLD: 8/13/16/24/32/48/64).
+static int launch_ragged(const RxParams& p, const RxLaunchCfg& cfg, hipStream_t s) {
+  const uint32_t g = cfg.grid_blocks, b = cfg.block_threads, l = cfg.lds_bytes;
+  int e;
+  switch (cfg.kernel) {
+    case RX_KERNEL_CSR_WAVE:
+      return cfg.stats ? launch_one(rx_csr_wave_kernel<true, true>, p, g, b, l, s) : launch_one(rx_csr_wave_kernel<false, true>, p, g, b, l, s);
+    case RX_KERNEL_SYM_WAVE:
+      return cfg.stats ? launch_one(rx_sym_wave_kernel<true, true>, p, g, b, l, s) : launch_one(rx_sym_wave_kernel<false, true>, p, g, b, l, s);
+    case RX_KERNEL_SYM_REG: {
+      const bool fold = cfg.fold && p.pin_tab;
+      const uint32_t lds = 64u * 4u;
+      if (cfg.reg_skip)
+        e = fold ? launch_one(rx_sym_reg_kernel<true, true, true>, p, p.n_streams, 64u, lds, s)
+                 : launch_one(rx_sym_reg_kernel<false, true, true>, p, p.n_streams, 64u, lds, s);
+      else
+        e = fold ? launch_one(rx_sym_reg_kernel<true, false, true>, p, p.n_streams, 64u, lds, s)
+                 : launch_one(rx_sym_reg_kernel<false, false, true>, p, p.n_streams, 64u, lds, s);
+      break;
+    }
+    case RX_KERNEL_SYM_PACK:
+      if (cfg.profile_pack) return (int)hipErrorInvalidValue;
+      if (cfg.fold && !cfg.stats && p.pin_tab) {
+        const size_t lds_cu = cfg.lds_per_cu ? cfg.lds_per_cu : 160u * 1024u;
+        switch (cfg.group_lanes) {  // (resolve_cfg: one of the FOLD builds' S)
+          case 8: e = launch_fold<8, true>(p, cfg, s, lds_cu); break;
+          case 13: e = launch_fold<13, true>(p, cfg, s, lds_cu); break;
+          case 16: e = launch_fold<16, true>(p, cfg, s, lds_cu); break;
+          case 24: e = launch_fold<24, true>(p, cfg, s, lds_cu); break;
+          case 32: e = launch_fold<32, true>(p, cfg, s, lds_cu); break;
+          case 48: e = launch_fold<48, true>(p, cfg, s, lds_cu); break;
+          case 64: e = launch_fold<64, true>(p, cfg, s, lds_cu); break;
+          default: return (int)hipErrorInvalidValue;
+        }
+        break;
+      }
+      switch (cfg.group_lanes) {
+        case 4: e = launch_pack<4, true>(p, cfg, s); break;
+        case 8: e = launch_pack<8, true>(p, cfg, s); break;
+        case 11: e = launch_pack<11, true>(p, cfg, s); break;
+        case 13: e = launch_pack<13, true>(p, cfg, s); break;
+        case 16: e = launch_pack<16, true>(p, cfg, s); break;
+        case 22: e = launch_pack<22, true>(p, cfg, s); break;
+        case 24: e = launch_pack<24, true>(p, cfg, s); break;
+        case 32: e = launch_pack<32, true>(p, cfg, s); break;
+        default: return (int)hipErrorInvalidValue;
+      }
+      break;
+    default:
+      return (int)hipErrorInvalidValue;
+  }
+  if (e) return e;
+  return launch_resume<true>(p, cfg, s);
 }
 
 // returns a hipError_t value (0 = hipSuccess)
 int rx_launch(const RxParams& p, const RxLaunchCfg& cfg, void* hip_stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   g_verbose = cfg.verbose;
+  if (p.slots) return launch_ragged(p, cfg, s);
   switch (cfg.kernel) {
     case RX_KERNEL_CSR_WAVE:
-      return cfg.stats ? launch_one(rx_csr_wave_kernel<true>, p, cfg.grid_blocks, cfg.block_threads, cfg.lds_bytes, s)
-                       : launch_one(rx_csr_wave_kernel<false>, p, cfg.grid_blocks, cfg.block_threads, cfg.lds_bytes, s);
+      return cfg.stats ? launch_one(rx_csr_wave_kernel<true, false>, p, cfg.grid_blocks, cfg.block_threads, cfg.lds_bytes, s)
+                       : launch_one(rx_csr_wave_kernel<false, false>, p, cfg.grid_blocks, cfg.block_threads, cfg.lds_bytes, s);
     case RX_KERNEL_SYM_WAVE:
-      return cfg.stats ? launch_one(rx_sym_wave_kernel<true>, p, cfg.grid_blocks, cfg.block_threads, cfg.lds_bytes, s)
-                       : launch_one(rx_sym_wave_kernel<false>, p, cfg.grid_blocks, cfg.block_threads, cfg.lds_bytes, s);
+      return cfg.stats ? launch_one(rx_sym_wave_kernel<true, false>, p, cfg.grid_blocks, cfg.block_threads, cfg.lds_bytes, s)
+                       : launch_one(rx_sym_wave_kernel<false, false>, p, cfg.grid_blocks, cfg.block_threads, cfg.lds_bytes, s);
     case RX_KERNEL_DFA:
     case RX_KERNEL_SYM_REG:
     case RX_KERNEL_SYM_PACK:
@@ -2515,11 +2801,11 @@ int rx_launch(const RxParams& p, const RxLaunchCfg& cfg, void* hip_stream) {
         const bool fold = cfg.fold && p.pin_tab;
         const uint32_t lds = 64u * 4u;  // the byte -> class map; the folding table is read with scalar loads
         if (cfg.reg_skip)
-          e = fold ? launch_one(rx_sym_reg_kernel<true, true>, p, p.n_streams, 64u, lds, s)
-                   : launch_one(rx_sym_reg_kernel<false, true>, p, p.n_streams, 64u, lds, s);
+          e = fold ? launch_one(rx_sym_reg_kernel<true, true, false>, p, p.n_streams, 64u, lds, s)
+                   : launch_one(rx_sym_reg_kernel<false, true, false>, p, p.n_streams, 64u, lds, s);
         else
-          e = fold ? launch_one(rx_sym_reg_kernel<true, false>, p, p.n_streams, 64u, lds, s)
-                   : launch_one(rx_sym_reg_kernel<false, false>, p, p.n_streams, 64u, lds, s);
+          e = fold ? launch_one(rx_sym_reg_kernel<true, false, false>, p, p.n_streams, 64u, lds, s)
+                   : launch_one(rx_sym_reg_kernel<false, false, false>, p, p.n_streams, 64u, lds, s);
       } else if (cfg.kernel == RX_KERNEL_DFA) {
         const uint32_t wpb = 4;
         const uint32_t grid = (p.n_streams + wpb * 64u - 1) / (wpb * 64u);
@@ -2556,16 +2842,7 @@ int rx_launch(const RxParams& p, const RxLaunchCfg& cfg, void* hip_stream) {
       if (e) return e;
       // second launch: the wave kernel finishes whatever the group kernel handed off (usually nothing;
       // the count is read on the device, so no host round-trip)
-      RxParams r = p;
-      r.resume = 1;
-      r.zero_next = nullptr;  // the first launch of the pair has done it
-      r.zero_words = 0;
-      const uint32_t wpb = cfg.block_threads / 64u;
-      uint32_t grid = (p.n_streams + wpb - 1) / wpb;
-      const uint32_t fill = (cfg.cu_count > 0 ? (uint32_t)cfg.cu_count : 256u) * 8u;  // enough blocks to fill the chip
-      if (grid > fill) grid = fill;
-      return cfg.stats ? launch_one(rx_sym_wave_kernel<true>, r, grid ? grid : 1, cfg.block_threads, cfg.lds_bytes, s)
-                       : launch_one(rx_sym_wave_kernel<false>, r, grid ? grid : 1, cfg.block_threads, cfg.lds_bytes, s);
+      return launch_resume<false>(p, cfg, s);
     }
     default:
       return (int)hipErrorInvalidValue;

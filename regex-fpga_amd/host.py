@@ -18,7 +18,7 @@ KERNEL_NAMES = {0: "auto", 1: "csr_wave", 2: "sym_wave", 3: "sym_group", 4: "sym
 
 # rx_opts.flags (A/B and diagnostic switches; read at plan creation, never from the environment)
 OPT_NO_PRUNE, OPT_FORCE_PRUNE, OPT_VERBOSE, OPT_PROFILE_PACK, OPT_NO_FOLD, OPT_FORCE_FOLD, OPT_REG_NO_SKIP = 1, 2, 4, 8, 16, 32, 64
-OPT_INJECT_RUN_FAULT, OPT_NO_PROBE = 128, 256
+OPT_INJECT_RUN_FAULT, OPT_NO_PROBE, OPT_RAGGED_NO_SORT = 128, 256, 512
 
 EVENT_DT = np.dtype([("stream", "<u4"), ("k", "<u4"), ("state", "<u4")])
 
@@ -69,7 +69,7 @@ ABI_SYMBOLS = ["rx_nfa_dfa_info", "rx_nfa_dfa_reset", "rx_compile_patterns", "rx
                "rx_match_sharded", "rx_plan_create", "rx_plan_upload", "rx_plan_set_device_input",
                "rx_plan_set_init_active", "rx_plan_launch", "rx_plan_sync", "rx_plan_kernel_times", "rx_plan_download", "rx_plan_free",
                "rx_device_count", "rx_device_name", "rx_plan_run", "rx_host_register", "rx_host_unregister", "rx_plan_tune",
-               "rx_plan_busy"]
+               "rx_plan_busy", "rx_match_ragged", "rx_plan_upload_ragged", "rx_plan_set_device_input_ragged"]
 
 _lib = None
 
@@ -140,6 +140,10 @@ def lib():
     if hasattr(L, "rx_plan_tune"):  # (an older build loaded through RX_LIBRARY_PATH for an A/B run has neither)
         L.rx_plan_tune.argtypes = [vp]
         L.rx_plan_busy.argtypes = [vp, C.POINTER(u32)]
+    if hasattr(L, "rx_match_ragged"):  # (likewise)
+        L.rx_match_ragged.argtypes = [vp, vp, vp, sz, vp, C.POINTER(_Opts), C.POINTER(_Result)]
+        L.rx_plan_upload_ragged.argtypes = [vp, vp, vp, sz]
+        L.rx_plan_set_device_input_ragged.argtypes = [vp, vp, vp, sz]
     L.rx_plan_sync.argtypes = [vp, C.POINTER(C.c_double)]
     L.rx_plan_kernel_times.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double)]
@@ -373,6 +377,61 @@ def match(nfa, data, mode=MODE_FULL, kernel=KERNEL_AUTO, device=-1, init_active=
     return out.as_dict()
 
 
+def ragged_batch(data, offsets=None):
+    """-> (uint8 bytes, uint64 offsets[n_streams + 1]) of a ragged batch: `data` is a list of byte arrays (offsets None),
+    or one uint8 array with `offsets` (stream s = data[offsets[s]:offsets[s+1]])."""
+    if offsets is None:
+        rows = [np.frombuffer(bytes(r), np.uint8) if isinstance(r, (bytes, bytearray, memoryview))
+                else np.asarray(r, dtype=np.uint8).reshape(-1) for r in data]
+        offsets = np.zeros(len(rows) + 1, np.uint64)
+        offsets[1:] = np.cumsum([r.size for r in rows], dtype=np.uint64)
+        data = np.concatenate(rows) if rows else np.zeros(0, np.uint8)
+    data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).reshape(-1))
+    offsets = _check_offsets(offsets)
+    if int(offsets[-1]) > data.size:  # (the library reads the host bytes up to offsets[-1]: it cannot check this)
+        raise ValueError(f"offsets end at {int(offsets[-1])}, past the {data.size} bytes of data")
+    return data, offsets
+
+
+def _check_offsets(offsets):
+    """offsets as uint64 [n_streams + 1]; negative values (which would wrap) and decreasing ones are refused here."""
+    o = np.asarray(offsets)
+    if o.ndim != 1 or o.size < 2:
+        raise ValueError("offsets must be [n_streams + 1]")
+    if o.dtype.kind not in "iu":
+        raise ValueError("offsets must be integers")
+    if o.dtype.kind == "i" and (o < 0).any():
+        raise ValueError("offsets must be non-negative")
+    o = np.ascontiguousarray(o, dtype=np.uint64)
+    if (o[1:] < o[:-1]).any():
+        raise ValueError("offsets must be non-decreasing")
+    return o
+
+
+def _ragged_len(offsets):
+    d = np.diff(offsets.astype(np.int64))
+    return int(d.max()) if d.size and (d >= 0).all() else 0
+
+
+def match_ragged(nfa, data, offsets=None, mode=MODE_FULL, kernel=KERNEL_AUTO, device=-1, init_active=None,
+                 events_cap=1 << 20, want_match_count=False, want_total=True, want_anymatch=True, want_final=True,
+                 collect_stats=False, k_base=0, group_lanes=0, flags=0):
+    """rx_match_ragged(): one-shot match of streams of different lengths (see ragged_batch for `data` / `offsets`).
+    Returns the same dict as match(); anymatch rows span the longest stream's passes, zero past each stream's own."""
+    data, offsets = ragged_batch(data, offsets)
+    ns = offsets.size - 1
+    out = _Out(nfa, ns, _ragged_len(offsets), mode, events_cap, want_match_count, want_total, want_anymatch, want_final)
+    o = _mk_opts(device, mode, kernel, None, k_base, collect_stats, group_lanes, flags)
+    ia = None
+    if init_active is not None:
+        ia = np.ascontiguousarray(init_active, dtype=np.uint64)
+        if ia.shape != (ns, nfa.nw64):
+            raise ValueError("init_active must be [n_streams, ceil(size/64)] uint64")
+    _chk(lib().rx_match_ragged(nfa._h, data.ctypes.data if data.size else None, offsets.ctypes.data, ns,
+                               ia.ctypes.data if ia is not None else None, C.byref(o), C.byref(out.r)), "rx_match_ragged")
+    return out.as_dict()
+
+
 def match_sharded(nfa, data, devices, mode=MODE_FULL, kernel=KERNEL_AUTO, events_cap=1 << 20,
                   want_match_count=False, want_total=True, want_anymatch=True, want_final=True, collect_stats=False,
                   group_lanes=0, flags=0):
@@ -416,6 +475,21 @@ class Plan:
         self._keep = keepalive
         _chk(lib().rx_plan_set_device_input(self._h, dptr, n_streams, stream_len, stride),
              "rx_plan_set_device_input")
+
+    def upload_ragged(self, data, offsets=None):
+        """rx_plan_upload_ragged(): a ragged batch (see ragged_batch) into the plan, the byte range in one copy."""
+        data, offsets = ragged_batch(data, offsets)
+        self.n_streams, self.stream_len = offsets.size - 1, _ragged_len(offsets)
+        _chk(lib().rx_plan_upload_ragged(self._h, data.ctypes.data if data.size else None, offsets.ctypes.data,
+                                         self.n_streams), "rx_plan_upload_ragged")
+
+    def set_device_input_ragged(self, dptr, offsets, keepalive=None):
+        """rx_plan_set_device_input_ragged(): stream s = device bytes [offsets[s], offsets[s+1]) from dptr (offsets: host)."""
+        offsets = _check_offsets(offsets)
+        self.n_streams, self.stream_len = offsets.size - 1, _ragged_len(offsets)
+        self._keep = keepalive
+        _chk(lib().rx_plan_set_device_input_ragged(self._h, dptr, offsets.ctypes.data, self.n_streams),
+             "rx_plan_set_device_input_ragged")
 
     def set_init_active(self, init_active):
         if init_active is None:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomized differential test: every kernel variant vs the CPU oracle on seeded random automata and inputs.
     python tools/fuzz_gpu.py --seconds 300 --seed 1
+    python tools/fuzz_gpu.py --seconds 300 --seed 1 --ragged   (ragged batches: random lengths and offsets per case)
 Writes progress lines (so a long run is not taken for hung) and stops at the first mismatch with a repro seed."""
 import argparse
 import importlib
@@ -15,6 +16,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from nfa_util import blowup_nfa, late_blowup_nfa, random_nfa  # noqa: E402
 from oracle import orx  # noqa: E402
+from ragged_util import ragged_ref  # noqa: E402
 
 rx = importlib.import_module("regex-fpga_amd")
 
@@ -22,6 +24,10 @@ KERNELS = [dict(kernel=rx.KERNEL_CSR_WAVE), dict(kernel=rx.KERNEL_SYM_WAVE)] + \
           [dict(kernel=rx.KERNEL_SYM_GROUP, group_lanes=g) for g in (1, 2, 4, 8, 16)] + \
           [dict(kernel=rx.KERNEL_SYM_PACK, group_lanes=s) for s in (2, 4, 8, 11, 12, 13, 16, 20, 22, 24, 32, 48, 64)] + \
           [dict(kernel=rx.KERNEL_SYM_REG), dict(kernel=rx.KERNEL_SYM_REG), dict(kernel=rx.KERNEL_DFA), dict(kernel=rx.KERNEL_AUTO)]
+# the kernels that take ragged batches (group_lanes run at the nearest instantiated S; FORCE_FOLD / FORCE_PRUNE drawn per run)
+RAGGED_KERNELS = [dict(kernel=rx.KERNEL_CSR_WAVE), dict(kernel=rx.KERNEL_SYM_WAVE)] + \
+                 [dict(kernel=rx.KERNEL_SYM_PACK, group_lanes=s) for s in (2, 4, 8, 11, 12, 13, 16, 20, 22, 24, 32, 48, 64)] + \
+                 [dict(kernel=rx.KERNEL_SYM_REG), dict(kernel=rx.KERNEL_AUTO)]
 
 
 def rand_regexes(rng, n):
@@ -38,7 +44,7 @@ def rand_regexes(rng, n):
     return out
 
 
-def one_case(rng, trial):
+def one_case(rng, trial, ragged=False):
     kind = int(rng.integers(6))
     if kind == 0:
         size = int(rng.integers(2, 600))
@@ -72,6 +78,8 @@ def one_case(rng, trial):
         rows = rng.choice(np.frombuffer(b"abcx0123 \n", np.uint8), size=(ns, sl))
     mode = int(rng.integers(2))
     CAP = 1 << 22
+    if ragged:
+        return ragged_case(rng, trial, kind, nfa, W, size, rows, mode, CAP)
     ref = orx.match_batch(W, size, rows, mode=mode, want_match_count=True, events_cap=CAP)
     overflow = ref["n_events"] > CAP  # then only the counters are comparable (device order is arrival order)
     ks = [KERNELS[i] for i in rng.choice(len(KERNELS), size=5, replace=False)] + [KERNELS[-1]]
@@ -105,19 +113,53 @@ def one_case(rng, trial):
     return None
 
 
+def ragged_case(rng, trial, kind, nfa, W, size, rows, mode, CAP):
+    """The case's bytes cut into streams of random lengths (0 ... 2 x the row length) at a random first offset."""
+    flat = rows.reshape(-1)
+    flat = np.concatenate([flat, flat[::-1], flat]) if flat.size else flat
+    ns = int(rng.integers(1, 130))
+    top = max(1, min(2 * rows.shape[1] + 1, 1 + flat.size // max(ns, 1)))
+    lens = rng.integers(0, top, ns)
+    first = int(rng.integers(0, 4))
+    off = np.zeros(ns + 1, np.uint64)
+    off[0] = first
+    off[1:] = first + np.cumsum(lens)
+    data = np.resize(flat, int(off[-1]) + 1).astype(np.uint8) if flat.size else np.zeros(int(off[-1]) + 1, np.uint8)
+    ref = ragged_ref(orx, W, size, data, off, mode, want_match_count=True)
+    if ref["n_events"] > CAP:
+        return None
+    for kern in [RAGGED_KERNELS[i] for i in rng.choice(len(RAGGED_KERNELS), size=4, replace=False)] + [RAGGED_KERNELS[-1]]:
+        stats = bool(rng.integers(2))
+        flags = (rx.host.OPT_REG_NO_SKIP if rng.integers(2) else 0) | (rx.host.OPT_RAGGED_NO_SORT if rng.integers(2) else 0) | \
+            (rx.host.OPT_FORCE_PRUNE if rng.integers(2) else 0) | (rx.host.OPT_FORCE_FOLD if rng.integers(2) else 0)
+        got = rx.match_ragged(nfa, data, off, mode=mode, want_match_count=True, collect_stats=stats, events_cap=CAP, flags=flags, **kern)
+        bad = [k for k in ("match_count", "final_active", "match_count_total") if not np.array_equal(got[k], ref[k])]
+        if got["n_events"] != ref["n_events"] or not np.array_equal(got["events"], ref["events"].astype(got["events"].dtype)):
+            bad.append("events")
+        if not np.array_equal(got["anymatch"][:, :ref["anymatch"].shape[1]], ref["anymatch"]) or got["anymatch"][:, ref["anymatch"].shape[1]:].any():
+            bad.append("anymatch")
+        if stats:
+            bad += [k for k in ("n_passes", "sum_active", "sum_edges", "alg_bytes") if got["stats"][k] != ref["stats"][k]]
+        if bad:
+            return (f"MISMATCH (ragged) trial {trial} kind {kind} size {size} ns {ns} lens {lens.tolist()[:16]} first {first} "
+                    f"mode {mode} kernel {kern} flags {flags} stats={stats} fields {bad}")
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first-trial", type=int, default=0)
     ap.add_argument("--n-trials", type=int, default=0)
+    ap.add_argument("--ragged", action="store_true", help="ragged batches on the kernels that take them")
     a = ap.parse_args()
     t0 = time.time()
     trial = a.first_trial
     last = t0
     while time.time() - t0 < a.seconds and (a.n_trials == 0 or trial < a.first_trial + a.n_trials):
         rng = np.random.default_rng([a.seed, trial])  # every case reproducible on its own
-        err = one_case(rng, trial)
+        err = one_case(rng, trial, a.ragged)
         if err:
             print(err, "seed", a.seed, flush=True)
             sys.exit(1)
