@@ -252,7 +252,31 @@ typedef struct rx_result {
   uint32_t final_states_overflow; /* out: 1 if the sets did not fit final_states_cap (final_cnt is exact, final_off then
                                      names only the part that was written) */
   uint32_t reserved0;
+  /* Match starts (the caller's struct_size must cover event_start; NULL = not wanted, and nothing is computed):
+   * event_start[i] = where the match of events[i] began, see RX_START_BEFORE.  Filled by rx_match, rx_match_ragged,
+   * rx_plan_download (uniform and ragged batches) and rx_match_sharded (per shard, concatenated like the events); with
+   * events_overflow they stay aligned to the events returned.  RX_EINVAL before any device work: event_start without an
+   * events array, and rx_plan_run (pipelined blocks: not supported).  rx_plan_download scans the launch's input backward:
+   * caller-owned device input (rx_plan_set_device_input*) must stay intact until the download, and once new input or a new
+   * start set has replaced the launched batch it returns RX_ESTATE.  Two downloads of one launch return the same starts.
+   * RX_ECAPACITY, before the scan, for automata whose bitmasks do not fit one wavefront's LDS (far beyond 65 536 states). */
+  uint32_t* event_start;     /* [events_cap] */
+  double start_ms;           /* out: hipEvent time of the start kernel, 0 when it did not run */
 } rx_result;
+
+/* Match starts.  Let S_0 be the stream's start set: {0} from reset, or the caller's start row.  Let u be the automaton's
+ * unanchored state, if it has one: the lowest-numbered state that has a self-edge on all 256 bytes AND that state 0 enters
+ * on all 256 bytes (state 1 of snort_16 and of compiled tables; l7 has none).  u is not always the pinned `.*` state of the
+ * kernels, which need only be fed by state 0 on most bytes.  The unanchored positions: P_0 = {0, u} & S_0; for m >= 1,
+ * P_m = {u} if 0 in S_0 or u in S_0, else empty.
+ * A match path of event (k, a) is q_0 .. q_k with q_0 in S_0, q_{m+1} in δ(q_m, c[m]), q_k = a.  The path's start is the
+ * largest m with q_m in P_m: the matched bytes are c[m .. k-1].  The event's start is the minimum over all its match paths,
+ * reported as k_base + m (the coordinates of rx_event.k; the match occupies [start, k)).  A path that touches no P_m began
+ * before this batch: if any path does that, the start is RX_START_BEFORE.  (k_base + passes <= 2^32 is enforced, so
+ * k_base + m never equals it.)  Outside the positions above a state of P is an ordinary state: the definition holds for
+ * tables without u, tables whose state 0 has in-edges and start sets without 0 or u, in every mode and for ragged streams
+ * (a stream's own bytes). */
+#define RX_START_BEFORE 0xFFFFFFFFu
 
 /* ---- one-shot match over host buffers ---------------------------------------------------- */
 /* bytes: n_streams rows of stream_len bytes, row s at bytes + s*stride.  init_active (optional,

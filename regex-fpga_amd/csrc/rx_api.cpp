@@ -136,11 +136,13 @@ struct DevTables {
   // lazy-DFA cache (allocated by the first RX_KERNEL_DFA launch)
   uint32_t *dfa_trans = nullptr, *dfa_pool = nullptr, *dfa_hash = nullptr, *dfa_hdr = nullptr;
   uint32_t dfa_pool_chunks = 0, dfa_hash_mask = 0;
+  // reverse slice index of the start scan (uploaded by the first request for match starts)
+  uint32_t *rev_off = nullptr, *rev = nullptr;
   int cu_count = 0;
   size_t lds_per_cu = 0;
-  std::array<uint32_t*, 14> bufs() const {
+  std::array<uint32_t*, 16> bufs() const {
     return {words, symidx, ovf, accept_bits, symidx_c, symidx_p, ovf_dir, pin_tab, regidx, byte_class,
-            dfa_trans, dfa_pool, dfa_hash, dfa_hdr};
+            dfa_trans, dfa_pool, dfa_hash, dfa_hdr, rev_off, rev};
   }
 };
 
@@ -164,6 +166,8 @@ struct rx_nfa {
   // AUTO, batches too small for a probe: do few of the cells the register kernel would place from hold lists?  (-1: not
   // looked at yet; the index is immutable, so the answer is computed once, under mu)
   int few_lists = -1;
+  // reverse slice index of the start scan, built under mu by the first request for match starts (rxh_build_reverse)
+  std::vector<uint32_t> rev_off, rev;
 };
 
 extern "C" int rx_nfa_from_words(const uint32_t* words, size_t nwords, uint32_t size_or_0, rx_nfa** out) {
@@ -396,6 +400,24 @@ extern "C" int rx_nfa_dfa_reset(const rx_nfa* cnfa, int device) {
   RX_CATCH
 }
 
+// ---- match starts: the reverse slice index, built and uploaded on the first request (like the DFA cache) ----
+static int ensure_start_tables(const rx_nfa* cnfa, int device, DevTables* out) {
+  rx_nfa* nfa = const_cast<rx_nfa*>(cnfa);
+  std::lock_guard<std::mutex> lk(nfa->mu);
+  DevTables& t = nfa->dev[device].t;
+  if (!t.rev_off) {
+    int rc;
+    if (nfa->rev_off.empty() && (rc = rxh_build_reverse(nfa->h, &nfa->rev_off, &nfa->rev))) return rc;
+    uint32_t *off = nullptr, *rev = nullptr;
+    if ((rc = upload_vec(nfa->rev_off, &off))) return rc;
+    if ((rc = upload_vec(nfa->rev, &rev))) { (void)hipFree(off); return rc; }
+    t.rev_off = off;
+    t.rev = rev;
+  }
+  *out = t;
+  return RX_OK;
+}
+
 // ---- plan -----------------------------------------------------------------------------------------
 struct rx_plan {
   const rx_nfa* nfa = nullptr;
@@ -429,6 +451,13 @@ struct rx_plan {
   bool have_init = false;             // start sets belong to ONE batch: every new input clears the flag
   std::vector<uint64_t> init_stage;   // host staging of the caller's start sets (tail bits masked)
   HipBuf<uint32_t> d_spill_streams, d_spill_k, d_spill_rows;
+  // match starts (rx_plan_download with rx_result.event_start): one start per captured event, device order; for a ragged
+  // batch the slot descriptor of every stream id; a hipEvent pair around the start kernel.  `start_input` is cleared when a
+  // start set is given after the launch (the scan must read the launch's own S_0)
+  HipBuf<uint32_t> d_starts;
+  HipBuf<RxSlot> d_by_id;
+  HipEvent st0, st1;
+  bool start_input = false;
   size_t am_stride = 0;
   // current batch
   size_t n_streams = 0, stream_len = 0, stride = 0;
@@ -766,6 +795,7 @@ extern "C" int rx_plan_set_device_input_ragged(rx_plan* p, const void* device_by
 extern "C" int rx_plan_set_init_active(rx_plan* p, const uint64_t* init_active) {
   RX_TRY
   if (!p) return RX_EINVAL;
+  p->start_input = false;  // (the launched batch's start sets are gone)
   if (!init_active) { p->have_init = false; return RX_OK; }
   if (!p->have_input) return RX_ESTATE;
   int dev;
@@ -1301,6 +1331,7 @@ extern "C" int rx_plan_launch(rx_plan* p) {
   HIPCHK(hipEventRecord(ev.second.e, p->stream));
   p->n_timed++;
   p->launched = true;
+  p->start_input = true;
   return RX_OK;
   RX_CATCH
 }
@@ -1390,40 +1421,50 @@ static bool ev_less(const rx_event& a, const rx_event& b) {
   if (a.k != b.k) return a.k < b.k;
   return a.state < b.state;
 }
+// an event with its match start: sorted as one record, so that the two stay aligned
+struct EvStart {
+  rx_event e;
+  uint32_t start;
+};
+static const rx_event& ev_of(const rx_event& e) { return e; }
+static const rx_event& ev_of(const EvStart& x) { return x.e; }
 
 // Canonical order (stream, k, state) of the events of streams [lo, lo + n_streams).  The device hands them over in
 // arrival order — per stream already ascending in k (a wavefront's passes allocate their slots one after the other) —
 // so a stable counting sort by stream does nearly everything in O(n); an insertion sort per stream finishes equal-k
 // runs and anything an unusual kernel left out of order.  (std::sort on 75 000 events took 5 ms of a 8 ms call.)
 // `src` (device order) -> `dst` in (stream, k, state) order; the two may not overlap
-static void sort_events_into(const rx_event* src, rx_event* dst, size_t n, uint32_t lo, size_t n_streams) {
+// (E: rx_event, or EvStart to carry the starts along)
+template <typename E>
+static void sort_events_into(const E* src, E* dst, size_t n, uint32_t lo, size_t n_streams) {
   if (n == 0) return;
+  auto less = [](const E& a, const E& b) { return ev_less(ev_of(a), ev_of(b)); };
   bool ok = n >= 64 && n_streams <= 8 * n + 1024;
   std::vector<uint32_t> at;
   if (ok) {
     at.assign(n_streams + 1, 0u);
     for (size_t i = 0; i < n && ok; i++) {
-      const rx_event& e = src[i];
+      const rx_event& e = ev_of(src[i]);
       if (e.stream < lo || e.stream - lo >= n_streams) ok = false;  // not ours: be safe
       else at[e.stream - lo + 1]++;
     }
   }
   if (!ok) {
-    memcpy(dst, src, n * sizeof(rx_event));
-    std::sort(dst, dst + n, ev_less);
+    memcpy(dst, src, n * sizeof(E));
+    std::sort(dst, dst + n, less);
     return;
   }
   for (size_t i = 0; i < n_streams; i++) at[i + 1] += at[i];
   {
     std::vector<uint32_t> pos(at.begin(), at.end() - 1);
-    for (size_t i = 0; i < n; i++) dst[pos[src[i].stream - lo]++] = src[i];
+    for (size_t i = 0; i < n; i++) dst[pos[ev_of(src[i]).stream - lo]++] = src[i];
   }
   for (size_t st = 0; st < n_streams; st++) {
     const uint32_t b = at[st], e = at[st + 1];
     for (uint32_t i = b + 1; i < e; i++) {
-      const rx_event x = dst[i];
+      const E x = dst[i];
       uint32_t j = i;
-      while (j > b && ev_less(x, dst[j - 1])) { dst[j] = dst[j - 1]; j--; }
+      while (j > b && less(x, dst[j - 1])) { dst[j] = dst[j - 1]; j--; }
       dst[j] = x;
     }
   }
@@ -1459,11 +1500,62 @@ static size_t result_bytes(const rx_result* res) {
   return res->struct_size ? std::min<size_t>(res->struct_size, sizeof(rx_result)) : RX_RESULT_ABI1_BYTES;
 }
 
+// the caller's event_start (NULL when its struct ends before start_ms)
+static uint32_t* starts_of(const rx_result* res) {
+  return result_bytes(res) >= offsetof(rx_result, start_ms) + sizeof(double) ? res->event_start : nullptr;
+}
+// event_start needs the events it is aligned with
+static bool starts_ok(const rx_result* res) {
+  return !starts_of(res) || (res->events && res->events_cap);
+}
+
+// Match starts of the launch's `n` captured events (device order, p->d_events) into starts[n] (host), and their kernel time.
+// Exact shortcut: no unanchored state, no edge back into state 0 and streams from reset — every start is position 0.
+static int plan_starts(rx_plan* p, size_t n, uint32_t* starts, double* ms) {
+  const RxHostNfa& h = p->nfa->h;
+  const RxParams& a = p->params;
+  *ms = 0;
+  if (h.unanch_state == 0xFFFFFFFFu && !h.state0_entered && !a.init_active) {
+    std::fill(starts, starts + n, a.k_base);
+    return RX_OK;
+  }
+  DevTables t;
+  int rc;
+  if ((rc = ensure_start_tables(p->nfa, p->device, &t))) return rc;
+  if ((rc = p->d_starts.grow(n))) return rc;
+  RxStartArgs sa{};
+  sa.events = p->d_events.p;
+  sa.n_events = (uint32_t)n;
+  sa.start = p->d_starts.p;
+  sa.rev_off = t.rev_off;
+  sa.rev = t.rev;
+  sa.unanch = h.unanch_state;
+  if (p->ragged) {  // the scan starts from an event's stream id: descriptors by id
+    std::vector<RxSlot> by_id(p->n_streams);
+    for (const RxSlot& d : p->slots) by_id[d.id] = d;
+    if ((rc = p->d_by_id.grow(p->n_streams))) return rc;
+    HIPCHK(hipMemcpyAsync(p->d_by_id.p, by_id.data(), p->n_streams * sizeof(RxSlot), hipMemcpyHostToDevice, p->stream));
+    sa.by_id = p->d_by_id.p;
+  }
+  if (!p->st0.e && ((rc = p->st0.create()) || (rc = p->st1.create()))) return rc;
+  HIPCHK(hipEventRecord(p->st0.e, p->stream));
+  const hipError_t e = (hipError_t)rx_launch_starts(a, sa, p->tab.cu_count, p->tab.lds_per_cu, p->stream);
+  if (e != hipSuccess) return hip_fail(e, "start kernel launch");
+  HIPCHK(hipEventRecord(p->st1.e, p->stream));
+  HIPCHK(hipMemcpyAsync(starts, p->d_starts.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));
+  float f = 0;
+  HIPCHK(hipEventElapsedTime(&f, p->st0.e, p->st1.e));
+  *ms = f;
+  return RX_OK;
+}
+
 static int plan_download(rx_plan* p, rx_result* res);
 
 extern "C" int rx_plan_download(rx_plan* p, rx_result* caller) {
   RX_TRY
   if (!p || !caller) return RX_EINVAL;
+  if (!starts_ok(caller)) return RX_EINVAL;
   rx_result full{};  // work on a full-size copy: fields behind the caller's struct_size are never written to it
   const size_t have = result_bytes(caller);
   memcpy(&full, caller, have);
@@ -1475,6 +1567,10 @@ extern "C" int rx_plan_download(rx_plan* p, rx_result* caller) {
 
 static int plan_download(rx_plan* p, rx_result* res) {
   if (!p->launched) return RX_ESTATE;
+  uint32_t* const want_starts = res->event_start;  // (a full-size copy: NULL unless the caller's struct has it)
+  res->start_ms = 0;
+  if (want_starts && !p->start_input) return RX_ESTATE;
+  if (want_starts && rx_start_capacity(p->nfa->h.size, p->tab.lds_per_cu)) return RX_ECAPACITY;
   int dev;
   int rc = bind_device(p->device, &dev);
   if (rc) return rc;
@@ -1515,7 +1611,23 @@ static int plan_download(rx_plan* p, rx_result* res) {
   const size_t captured = (size_t)std::min<unsigned long long>(cnt[0], p->events_cap);
   res->events_overflow = cnt[0] > p->events_cap ? 1u : 0u;
   res->n_events = 0;
-  if (res->events && res->events_cap && captured) {
+  if (res->events && res->events_cap && captured && want_starts) {
+    // starts of every captured event, then events and starts sorted as one record
+    std::vector<uint32_t> starts(captured);
+    if ((rc = plan_starts(p, captured, starts.data(), &res->start_ms))) return rc;
+    std::vector<rx_event> ev(captured);
+    HIPCHK(hipMemcpy(ev.data(), p->d_events.p, captured * sizeof(rx_event), hipMemcpyDeviceToHost));
+    std::vector<EvStart> tmp(captured), sorted(captured);
+    for (size_t i = 0; i < captured; i++) tmp[i] = EvStart{ev[i], starts[i]};
+    sort_events_into(tmp.data(), sorted.data(), captured, p->params.stream_base, p->n_streams);
+    const size_t n = std::min(captured, res->events_cap);
+    for (size_t i = 0; i < n; i++) {
+      res->events[i] = sorted[i].e;
+      want_starts[i] = sorted[i].start;
+    }
+    res->n_events = n;
+    if (captured > res->events_cap) res->events_overflow = 1u;
+  } else if (res->events && res->events_cap && captured) {
     std::vector<rx_event> tmp(captured), sorted(captured);
     HIPCHK(hipMemcpy(tmp.data(), p->d_events.p, captured * sizeof(rx_event), hipMemcpyDeviceToHost));
     sort_events_into(tmp.data(), sorted.data(), captured, p->params.stream_base, p->n_streams);  // device order is arrival order; canonical = (stream,k,state)
@@ -1571,6 +1683,7 @@ extern "C" int rx_plan_run(rx_plan* p, const uint8_t* bytes, size_t n_streams, s
                            rx_result* caller) {
   RX_TRY
   if (!p || !caller || (!bytes && stream_len)) return RX_EINVAL;
+  if (starts_of(caller)) return RX_EINVAL;  // (match starts: rx_plan_download only, the pipelined blocks have none)
   rx_result full{};
   const size_t have = result_bytes(caller);
   memcpy(&full, caller, have);
@@ -1847,10 +1960,13 @@ extern "C" int rx_match(const rx_nfa* nfa, const uint8_t* bytes, size_t n_stream
   RX_TRY
   if (!nfa || !res || (!bytes && stream_len) || n_streams == 0 || stride < stream_len) return RX_EINVAL;
   if (read_opts(opts).k_base + passes_for(stream_len, RX_MODE_FULL) > (1ull << 32)) return RX_EINVAL;
+  if (!starts_ok(res)) return RX_EINVAL;
   rx_plan* p = nullptr;
-  // (compact final sets: only when the caller's struct has the fields, and only on the pipelined path below)
+  // (compact final sets: only when the caller's struct has the fields, and only on the pipelined path below; match starts
+  // take the non-pipelined one, whose download has the launch's input at hand)
   const bool has_compact = result_bytes(res) >= offsetof(rx_result, final_states_overflow) + sizeof(uint32_t);
-  if (has_compact && res->final_states && init_active) return RX_EINVAL;
+  const bool starts = starts_of(res) != nullptr;
+  if (has_compact && res->final_states && (init_active || starts)) return RX_EINVAL;
   int rc = rx_plan_create(nfa, opts, n_streams, stream_len, res->events ? res->events_cap : 0,
                           res->match_count != nullptr, res->anymatch != nullptr,
                           res->final_active != nullptr || (has_compact && res->final_states != nullptr), &p);
@@ -1859,7 +1975,8 @@ extern "C" int rx_match(const rx_nfa* nfa, const uint8_t* bytes, size_t n_stream
     rx_plan_free(p);
     return code;
   };
-  if (!init_active) {
+  if (starts && rx_start_capacity(nfa->h.size, p->tab.lds_per_cu)) return done(RX_ECAPACITY);
+  if (!init_active && !starts) {
     // streams from reset: the pipelined path (blocks of streams, upload / kernel / download overlapped)
     const auto w0 = std::chrono::steady_clock::now();
     rc = rx_plan_run(p, bytes, n_streams, stream_len, stride, res);
@@ -1878,7 +1995,7 @@ extern "C" int rx_match(const rx_nfa* nfa, const uint8_t* bytes, size_t n_stream
   if (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess) return done2(RX_EHIP);
   (void)hipEventRecord(t0, p->stream);
   if ((rc = rx_plan_upload(p, bytes, n_streams, stream_len, stride))) return done2(rc);
-  if ((rc = rx_plan_set_init_active(p, init_active))) return done2(rc);
+  if (init_active && (rc = rx_plan_set_init_active(p, init_active))) return done2(rc);
   (void)hipEventRecord(t1, p->stream);
   if ((rc = rx_plan_launch(p))) return done2(rc);
   if ((rc = rx_plan_sync(p, nullptr))) return done2(rc);
@@ -1905,6 +2022,7 @@ extern "C" int rx_match_ragged(const rx_nfa* nfa, const uint8_t* bytes, const ui
   const bool has_compact = result_bytes(res) >= offsetof(rx_result, final_states_overflow) + sizeof(uint32_t);
   if (has_compact && (res->final_states || res->final_off || res->final_cnt)) return RX_EINVAL;
   if (res->anymatch && res->anymatch_stride < (size_t)((passes_for(longest, o.mode) + 31) / 32)) return RX_EINVAL;
+  if (!starts_ok(res)) return RX_EINVAL;
   rx_plan* p = nullptr;
   int rc = rx_plan_create(nfa, opts, n_streams, longest, res->events ? res->events_cap : 0,
                           res->match_count != nullptr, res->anymatch != nullptr, res->final_active != nullptr, &p);
@@ -1913,6 +2031,7 @@ extern "C" int rx_match_ragged(const rx_nfa* nfa, const uint8_t* bytes, const ui
     rx_plan_free(p);
     return code;
   };
+  if (starts_of(res) && rx_start_capacity(nfa->h.size, p->tab.lds_per_cu)) return done(RX_ECAPACITY);
   hipEvent_t t0 = nullptr, t1 = nullptr;
   auto done2 = [&](int code) {
     if (t0) (void)hipEventDestroy(t0);
@@ -1946,6 +2065,8 @@ extern "C" int rx_match_sharded(const rx_nfa* nfa, const uint8_t* bytes, size_t 
   // (the list form of the final sets is per device; the sharded call returns rows)
   if (result_bytes(res) >= offsetof(rx_result, final_states_overflow) + sizeof(uint32_t) && (res->final_states || res->final_off || res->final_cnt))
     return RX_EINVAL;
+  if (!starts_ok(res)) return RX_EINVAL;
+  uint32_t* const want_starts = starts_of(res);
   const int nd = (int)std::min<size_t>((size_t)n_devices, n_streams);
   const uint32_t size = nfa->h.size;
   const size_t nw64 = ((size_t)size + 63) / 64;
@@ -1953,6 +2074,7 @@ extern "C" int rx_match_sharded(const rx_nfa* nfa, const uint8_t* bytes, size_t 
     size_t s0 = 0, n = 0;
     rx_result r{};
     std::vector<rx_event> ev;
+    std::vector<uint32_t> start;
     std::vector<uint64_t> mct;
     int rc = RX_OK;
     std::string err;
@@ -1979,6 +2101,10 @@ extern "C" int rx_match_sharded(const rx_nfa* nfa, const uint8_t* bytes, size_t 
         x.ev.resize(res->events_cap);
         x.r.events = x.ev.data();
         x.r.events_cap = res->events_cap;
+        if (want_starts) {
+          x.start.resize(res->events_cap);
+          x.r.event_start = x.start.data();
+        }
       }
       if (res->match_count) x.r.match_count = res->match_count + x.s0 * size;
       if (res->match_count_total) { x.mct.assign(size, 0); x.r.match_count_total = x.mct.data(); }
@@ -1996,6 +2122,7 @@ extern "C" int rx_match_sharded(const rx_nfa* nfa, const uint8_t* bytes, size_t 
   }
   res->n_events = 0;
   res->events_overflow = 0;
+  if (want_starts) res->start_ms = 0;
   if (res->match_count_total) memset(res->match_count_total, 0, (size_t)size * sizeof(uint64_t));
   for (int d = 0; d < nd; d++) {
     Shard& x = sh[d];
@@ -2004,6 +2131,7 @@ extern "C" int rx_match_sharded(const rx_nfa* nfa, const uint8_t* bytes, size_t 
       if (res->n_events < res->events_cap) {
         rx_event ev = x.r.events[e];
         ev.stream += (uint32_t)x.s0;
+        if (want_starts) want_starts[res->n_events] = x.r.event_start[e];
         res->events[res->n_events++] = ev;
       } else {
         res->events_overflow = 1;
@@ -2022,6 +2150,7 @@ extern "C" int rx_match_sharded(const rx_nfa* nfa, const uint8_t* bytes, size_t 
     res->stats.d2h_ms = std::max(res->stats.d2h_ms, x.r.stats.d2h_ms);
     res->stats.kernel_used = x.r.stats.kernel_used;
     if (result_bytes(res) >= offsetof(rx_result, stats) + sizeof(rx_stats)) { res->stats.lanes_used = x.r.stats.lanes_used; res->stats.variant = x.r.stats.variant; }
+    if (want_starts) res->start_ms = std::max(res->start_ms, x.r.start_ms);  // slowest device
     res->stats.n_launches += x.r.stats.n_launches;
     res->stats.tb_cycles += x.r.stats.tb_cycles;  // pairs never straddle shards when every shard is even-sized
   }

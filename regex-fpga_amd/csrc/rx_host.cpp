@@ -165,6 +165,27 @@ int rxh_build(const uint32_t* W, size_t nwords, uint32_t size_or_0, RxHostNfa* o
       if (nself == 256) { best = fed[i]; out->pin_state = i; }
     }
   }
+  // ---- unanchored state u of the start scan (not always pin_state: that one need only be fed on MOST bytes) ----
+  out->unanch_state = 0xFFFFFFFFu;
+  out->state0_entered = false;
+  {
+    for (uint32_t j = rp[1]; j < out->nnz && !out->state0_entered; j++) out->state0_entered = (col[j] & 0xFFFFFFu) == 0;
+    for (uint32_t j = rp[0]; j < rp[1] && !out->state0_entered; j++) out->state0_entered = (col[j] & 0xFFFFFFu) == 0;
+    std::map<uint32_t, std::vector<bool>> from0;  // target of state 0 -> the bytes it is entered on
+    for (uint32_t j = rp[0]; j < rp[1]; j++) {
+      auto& b = from0[col[j] & 0xFFFFFFu];
+      if (b.empty()) b.assign(256, false);
+      b[col[j] >> 24] = true;
+    }
+    for (const auto& kv : from0) {  // ascending state ids: the first that qualifies is u
+      const uint32_t i = kv.first;
+      if (std::count(kv.second.begin(), kv.second.end(), true) != 256) continue;
+      std::vector<bool> self(256, false);
+      for (uint32_t j = rp[i]; j < rp[i + 1]; j++)
+        if ((col[j] & 0xFFFFFFu) == i) self[col[j] >> 24] = true;
+      if (std::count(self.begin(), self.end(), true) == 256) { out->unanch_state = i; break; }
+    }
+  }
   const uint32_t pin = out->pin_state;
   auto pin_flag = [&](uint32_t t) { return t == pin ? RXE_PIN : 0u; };
 
@@ -441,5 +462,29 @@ int rxh_build(const uint32_t* W, size_t nwords, uint32_t size_or_0, RxHostNfa* o
         }
     }
   }
+  return RX_OK;
+}
+
+int rxh_build_reverse(const RxHostNfa& h, std::vector<uint32_t>* off, std::vector<uint32_t>* preds) {
+  const uint32_t* rp = h.row_ptr();
+  const uint32_t* col = h.col();
+  const size_t nc = h.n_classes, cells = (size_t)h.size * nc;
+  // one entry per (target, class, source): several symbols of one class on one edge pair collapse into one
+  std::vector<uint64_t> trip;
+  trip.reserve(h.nnz);
+  for (uint32_t q = 0; q < h.size; q++)
+    for (uint32_t j = rp[q]; j < rp[q + 1]; j++) {
+      const uint64_t t = col[j] & 0xFFFFFFu, c = h.byte_class[col[j] >> 24];
+      trip.push_back(((t * nc + c) << 24) | q);
+    }
+  std::sort(trip.begin(), trip.end());
+  trip.erase(std::unique(trip.begin(), trip.end()), trip.end());
+  off->assign(cells + 1, 0u);
+  preds->resize(trip.size());
+  for (size_t i = 0; i < trip.size(); i++) {
+    (*off)[(trip[i] >> 24) + 1]++;
+    (*preds)[i] = (uint32_t)(trip[i] & 0xFFFFFFu);
+  }
+  for (size_t i = 0; i < cells; i++) (*off)[i + 1] += (*off)[i];
   return RX_OK;
 }

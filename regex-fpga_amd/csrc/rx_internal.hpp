@@ -174,6 +174,19 @@ struct RxLaunchCfg {
   bool profile_pack;       // rx_opts.flags & RX_OPT_PROFILE_PACK: stamped diagnostic build of the pack kernel (S=16)
 };
 
+// The start scan (rx_start_kernel): one wavefront per captured accept event walks the transposed automaton backward from
+// the event over the bytes the launch described by RxParams read (rxmatch.h, RX_START_BEFORE).  Its list + bitmask carve is
+// the wave kernels' (RxParams::nw32 / lds_words_per_stream, set by rx_launch_starts).
+struct RxStartArgs {
+  const rx_event* events;      // the launch's captured events, device order
+  uint32_t n_events;
+  uint32_t* start;             // [n_events] out: k_base + m, or RX_START_BEFORE
+  const uint32_t* rev_off;     // rxh_build_reverse
+  const uint32_t* rev;
+  const RxSlot* by_id;         // ragged batch: the slot descriptor of every stream id (null for a uniform batch)
+  uint32_t unanch;             // RxHostNfa::unanch_state
+};
+
 // rx_kernels.hip
 int rx_pick_launch(uint32_t kernel, uint32_t size, uint32_t n_streams, int cu_count, size_t lds_per_cu,
                    RxParams* p, RxLaunchCfg* cfg);
@@ -181,6 +194,9 @@ int rx_launch(const RxParams& p, const RxLaunchCfg& cfg, void* hip_stream);
 // Final sets as compact lists: rows[n_streams][row_words] (bitmask rows as the kernels leave them) -> per stream its states
 // in ascending order at states[off[s] .. off[s] + cnt[s]); off is relative to `states`; *counter (zero before the launch)
 // ends as the number of entries the sets need, entries beyond `cap` are not written.
+// RX_ECAPACITY when one wavefront's bitmasks do not fit a CU's LDS (checked before anything is enqueued)
+int rx_start_capacity(uint32_t size, size_t lds_per_cu);
+int rx_launch_starts(const RxParams& p, const RxStartArgs& a, int cu_count, size_t lds_per_cu, void* hip_stream);
 int rx_launch_final_compact(const uint32_t* rows, uint32_t n_streams, uint32_t row_words, uint32_t* states, uint32_t cap,
                             uint32_t* off, uint32_t* cnt, unsigned long long* counter, void* hip_stream);
 
@@ -208,6 +224,10 @@ struct RxHostNfa {
   // RxParams::regidx; empty for automata whose table would exceed 256 MB (the register kernel is then not offered)
   std::vector<uint32_t> regidx;
   uint32_t reg_tmask = RXE_TGT_MASK;  // RxParams::reg_tmask
+  // Match starts (rxmatch.h, RX_START_BEFORE): the unanchored state u — the lowest-numbered state with a self-edge on all 256
+  // bytes that state 0 enters on all 256 bytes (none: 0xFFFFFFFF) — and whether any edge leads back into state 0
+  uint32_t unanch_state = 0xFFFFFFFFu;
+  bool state0_entered = false;
   const uint32_t* row_ptr() const { return words.data(); }
   const uint32_t* col() const { return words.data() + size + 1; }
 };
@@ -217,6 +237,10 @@ int rxh_read_file(const char* path, std::string* out);
 int rxh_infer_size(const uint32_t* W, size_t nwords, uint32_t* size);
 int rxh_validate(const uint32_t* W, size_t nwords, uint32_t size);
 int rxh_build(const uint32_t* W, size_t nwords, uint32_t size_or_0, RxHostNfa* out);
+// Reverse slice index of the start scan: the predecessors of state t on byte class c are preds[off[t * n_classes + c] ..
+// off[t * n_classes + c + 1]), ascending.  The forward byte classes hold in reverse: bytes whose slice-index columns are equal
+// have equal predecessor sets.
+int rxh_build_reverse(const RxHostNfa& h, std::vector<uint32_t>* off, std::vector<uint32_t>* preds);
 // rx_compile.cpp
 int rxc_compile(const char* const* patterns, size_t n, uint32_t flags, std::vector<uint32_t>* words,
                 std::vector<int32_t>* accept_pattern, std::string* err);

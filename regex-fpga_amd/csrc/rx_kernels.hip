@@ -2574,6 +2574,118 @@ __global__ void __launch_bounds__(1024) rx_final_compact_kernel(const uint32_t* 
   }
 }
 
+// =================================================================================================
+// Match starts (rxmatch.h, RX_START_BEFORE): one wavefront per captured accept event
+// =================================================================================================
+// Event (k, a) of stream s: R = {a} \ P_k, then for m = k-1 .. 0 the predecessors of R on byte class c[m] (reverse slice
+// index, rxh_build_reverse); those in P_m record candidate m and stop there, the rest form the next R.  The last candidate
+// recorded is the smallest; a set that is still alive at m = 0 and meets S_0 means a path that began before the batch.
+// The set is the wave kernels' list + bitmask pair (StreamState: exact dedup through ds_or on the bitmask, the dense form
+// beyond the list's capacity), so a start never depends on scheduling.  The byte classes of 256 bytes are loaded one chunk
+// ahead of the dependent chain (set -> predecessor gather -> dedup) and broadcast from a lane per step.
+template <bool RAGGED>
+__global__ void __launch_bounds__(256) rx_start_kernel(const RxParams p, const RxStartArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wib = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+  uint32_t* my = lds + (size_t)wib * p.lds_words_per_stream;
+  StreamState st;
+  st.cb = my;
+  st.nb = my + p.nw32;
+  st.clist = st.nb + p.nw32;
+  st.cap = (p.lds_words_per_stream - 2u * p.nw32) >> 1;
+  st.nlist = st.clist + st.cap;
+  for (uint32_t w = lane; w < 2u * p.nw32; w += 64u) my[w] = 0u;
+  wave_sync();
+  const uint8_t* __restrict__ cls_of = reinterpret_cast<const uint8_t*>(p.byte_class);
+  const uint32_t* __restrict__ rev_off = a.rev_off;
+  const uint32_t* __restrict__ rev = a.rev;
+  const uint32_t nc = p.n_classes, u = a.unanch;
+  auto classes = [&](uint32_t w) {  // the class ids of a dword's four bytes, one per byte
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; b++) r |= (uint32_t)cls_of[(w >> (8u * b)) & 0xFFu] << (8u * b);
+    return r;
+  };
+
+  for (uint32_t i = blockIdx.x * wpb + wib; i < a.n_events; i += gridDim.x * wpb) {
+    const rx_event ev = a.events[i];
+    const uint32_t id = ev.stream - p.stream_base, k = ev.k - p.k_base;
+    std::conditional_t<RAGGED, RaggedFeed, ByteFeed> feed;
+    bool ok = id < p.n_streams;
+    if (ok) {
+      if constexpr (RAGGED) {
+        const RxSlot d = a.by_id[id];
+        feed.base = p.bytes + d.off;
+        feed.len = d.len;
+      } else {
+        feed.base = p.bytes + (size_t)id * p.stride;
+        feed.len = p.stream_len;
+        feed.aligned = ((reinterpret_cast<uintptr_t>(feed.base)) & 3u) == 0;
+      }
+      ok = k <= feed.len;
+    }
+    if (!ok) {  // (not an event of this launch: nothing of its stream is read)
+      if (lane == 0) a.start[i] = RX_START_BEFORE;
+      continue;
+    }
+    const uint32_t* init_row = p.init_active ? p.init_active + (size_t)id * p.nw64x2 : nullptr;
+    auto in_s0 = [&](uint32_t q) { return init_row ? ((init_row[q >> 5] >> (q & 31u)) & 1u) != 0u : q == 0u; };
+    const bool u_live = u != 0xFFFFFFFFu && (in_s0(0u) || in_s0(u));
+    auto in_p = [&](uint32_t q, uint32_t m) { return m ? (q == u && u_live) : ((q == 0u || q == u) && in_s0(q)); };
+
+    uint32_t cand = RX_START_BEFORE;  // the smallest position at which a path met P so far
+    st.n_next = 0;
+    st.dense = false;
+    if (in_p(ev.state, k)) {
+      cand = k;
+      st.n_cur = 0;
+    } else {
+      if (lane == 0) st.clist[0] = ev.state;
+      st.n_cur = 1;
+    }
+    wave_sync();
+    uint32_t m = k, cur_cls = 0, nxt_cls = k ? classes(feed.load_chunk((k - 1u) >> 8, lane)) : 0u;
+    while ((st.n_cur || st.dense) && m > 0u) {
+      m--;
+      if ((m & 255u) == 255u || m + 1u == k) {
+        cur_cls = nxt_cls;
+        if (m >> 8) nxt_cls = classes(feed.load_chunk((m >> 8) - 1u, lane));
+      }
+      const uint32_t c = (bcast(cur_cls, (m >> 2) & 63u) >> ((m & 3u) * 8u)) & 0xFFu;
+      bool hit = false;
+      for_each_active<false>(p, st, lane, [&](bool valid, uint32_t s) {
+        uint32_t j = 0, end = 0;
+        if (valid) {
+          const size_t cell = (size_t)s * nc + c;
+          j = rev_off[cell];
+          end = rev_off[cell + 1];
+        }
+        while (wballot(j < end)) {
+          const bool act = j < end;
+          const uint32_t q = act ? rev[j] : 0u;
+          const bool met = act && in_p(q, m);
+          hit |= met;
+          emit_target(st, act && !met, q, lane);
+          j++;
+        }
+      });
+      if (wballot(hit)) cand = m;
+      stream_swap(p, st, lane);
+    }
+    bool before = false;
+    if (st.n_cur || st.dense) {  // alive at m = 0: a path from S_0 that met no P began before the batch
+      bool any = false;
+      for_each_active<false>(p, st, lane, [&](bool valid, uint32_t s) { any |= valid && in_s0(s); });
+      before = wballot(any) != 0u;
+    }
+    if (lane == 0) a.start[i] = (before || cand == RX_START_BEFORE) ? RX_START_BEFORE : p.k_base + cand;
+    if (st.dense)
+      for (uint32_t w = lane; w < p.nw32; w += 64u) st.cb[w] = 0u;
+    wave_sync();
+  }
+}
+
 }  // namespace
 
 int rx_launch_final_compact(const uint32_t* rows, uint32_t n_streams, uint32_t row_words, uint32_t* states, uint32_t cap,
@@ -2582,6 +2694,39 @@ int rx_launch_final_compact(const uint32_t* rows, uint32_t n_streams, uint32_t r
   hipLaunchKernelGGL(rx_final_compact_kernel, dim3((n_streams + 15u) / 16u), dim3(1024), 0, reinterpret_cast<hipStream_t>(hip_stream), rows,
                      n_streams, row_words, states, cap, off, cnt, counter);
   return (int)hipGetLastError();
+}
+
+
+// ---- match starts ----------------------------------------------------------------------------------
+// One wavefront's carve (two bitmasks + two lists of at least RX_LIST_CAP entries) must fit a CU's LDS.
+int rx_start_capacity(uint32_t size, size_t lds_per_cu) {
+  const size_t nw32 = ((size_t)size + 31u) / 32u;
+  return (2u * nw32 + 2u * RX_LIST_CAP) * 4u <= lds_per_cu ? RX_OK : RX_ECAPACITY;
+}
+
+int rx_launch_starts(const RxParams& launched, const RxStartArgs& a, int cu_count, size_t lds_per_cu, void* hip_stream) {
+  if (a.n_events == 0) return 0;
+  RxParams p = launched;  // the launch's batch (bytes, slots, start rows, k_base); the carve is the start kernel's own
+  const uint32_t nw32 = (p.size + 31u) / 32u;
+  uint32_t cap = 256u;  // snort_16's largest backward set is 74 states; larger sets run in the dense form
+  while (cap > RX_LIST_CAP && (size_t)(2u * nw32 + 2u * cap) * 4u * 4u > lds_per_cu / 2) cap >>= 1;
+  p.nw32 = nw32;
+  p.lds_words_per_stream = 2u * nw32 + 2u * cap;
+  const size_t per_wave = (size_t)p.lds_words_per_stream * 4u;
+  uint32_t wpb = 4;
+  while (wpb > 1 && per_wave * wpb > lds_per_cu / 2) wpb >>= 1;
+  const uint32_t lds = (uint32_t)(per_wave * wpb);
+  const uint32_t grid = std::min<uint32_t>((a.n_events + wpb - 1u) / wpb, (uint32_t)std::max(cu_count, 1) * 256u);
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  auto go = [&](auto kern) -> int {
+    if (lds > 64u * 1024u) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(wpb * 64u), lds, s, p, a);
+    return (int)hipGetLastError();
+  };
+  return p.slots ? go(rx_start_kernel<true>) : go(rx_start_kernel<false>);
 }
 
 // -------------------------------------------------------------------------------------------------

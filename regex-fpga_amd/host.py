@@ -53,7 +53,10 @@ class _Result(C.Structure):
                 ("final_active", C.c_void_p), ("stats", _Stats),
                 ("final_states", C.c_void_p), ("final_off", C.c_void_p), ("final_cnt", C.c_void_p),
                 ("final_states_cap", C.c_size_t), ("n_final_states", C.c_size_t), ("final_states_overflow", C.c_uint32),
-                ("reserved0", C.c_uint32)]
+                ("reserved0", C.c_uint32), ("event_start", C.c_void_p), ("start_ms", C.c_double)]
+
+# rx_result.event_start: the match began before the batch (a chained stream's earlier part); see include/rxmatch.h
+START_BEFORE = 0xFFFFFFFF
 
 
 class _Info(C.Structure):
@@ -278,7 +281,7 @@ class _Out:
     """Caller-allocated output arrays for one rx_result."""
 
     def __init__(self, nfa, n_streams, stream_len, mode, events_cap, want_match_count, want_total, want_anymatch,
-                 want_final, compact_final=0):
+                 want_final, compact_final=0, starts=False):
         self.npass = n_passes(stream_len, mode)
         self.ev = np.zeros(max(events_cap, 1), dtype=EVENT_DT) if events_cap else None
         self.mc = np.zeros((n_streams, nfa.size), np.uint32) if want_match_count else None
@@ -291,6 +294,8 @@ class _Out:
         self.fst = np.zeros(compact_final, np.uint32) if compact_final else None
         self.foff = np.zeros(n_streams, np.uint32) if compact_final else None
         self.fcnt = np.zeros(n_streams, np.uint32) if compact_final else None
+        # starts: the match start of every returned event (rx_result.event_start, aligned with the events)
+        self.st = np.zeros(max(events_cap, 1), np.uint32) if starts else None
         r = _Result()
         r.struct_size = C.sizeof(_Result)
         if self.ev is not None:
@@ -306,6 +311,8 @@ class _Out:
         if self.fst is not None:
             r.final_states, r.final_off, r.final_cnt = self.fst.ctypes.data, self.foff.ctypes.data, self.fcnt.ctypes.data
             r.final_states_cap = compact_final
+        if self.st is not None:
+            r.event_start = self.st.ctypes.data
         self.r = r
 
     def as_dict(self):
@@ -315,11 +322,12 @@ class _Out:
                     anymatch=self.am[:, :max((self.npass + 31) // 32, 1)] if self.am is not None else None, final_active=self.fin,
                     final_states=self.fst[:r.n_final_states] if self.fst is not None else None, final_off=self.foff,
                     final_cnt=self.fcnt, final_states_overflow=bool(r.final_states_overflow),
+                    start=self.st[:r.n_events] if self.st is not None else None,
                     stats=dict(n_passes=int(s.n_passes), n_events=int(s.n_events), sum_active=int(s.sum_active),
                                sum_edges=int(s.sum_edges), alg_bytes=int(s.alg_bytes), kernel_ms=s.kernel_ms,
                                h2d_ms=s.h2d_ms, d2h_ms=s.d2h_ms, kernel_used=int(s.kernel_used),
                                n_launches=int(s.n_launches), tb_cycles=int(s.tb_cycles), lanes_used=int(s.lanes_used),
-                               variant=_variant_name(s)))
+                               variant=_variant_name(s), start_ms=r.start_ms))
 
 
 def expand_final(res, nw64):
@@ -360,12 +368,15 @@ def _as_rows(data):
 
 def match(nfa, data, mode=MODE_FULL, kernel=KERNEL_AUTO, device=-1, init_active=None, events_cap=1 << 20,
           want_match_count=False, want_total=True, want_anymatch=True, want_final=True, collect_stats=False,
-          k_base=0, group_lanes=0, flags=0, compact_final=0):
+          k_base=0, group_lanes=0, flags=0, compact_final=0, starts=False):
     """rx_match(): one-shot match of uint8 [n_streams, stream_len] host rows on one GPU.  compact_final = N: the final
-    sets as lists of at most N states in all (see Plan.run) instead of bitmask rows; streams from reset only."""
+    sets as lists of at most N states in all (see Plan.run) instead of bitmask rows; streams from reset only.
+    starts=True: out["start"] (np.uint32, aligned with out["events"]) = where each match began, START_BEFORE for a match
+    that began before the batch; stats["start_ms"] = the start kernel's time."""
     data, stride = _as_rows(data)
     ns, sl = data.shape
-    out = _Out(nfa, ns, sl, mode, events_cap, want_match_count, want_total, want_anymatch, want_final, compact_final)
+    out = _Out(nfa, ns, sl, mode, events_cap, want_match_count, want_total, want_anymatch, want_final, compact_final,
+               starts=starts)
     o = _mk_opts(device, mode, kernel, None, k_base, collect_stats, group_lanes, flags)
     ia = None
     if init_active is not None:
@@ -415,12 +426,13 @@ def _ragged_len(offsets):
 
 def match_ragged(nfa, data, offsets=None, mode=MODE_FULL, kernel=KERNEL_AUTO, device=-1, init_active=None,
                  events_cap=1 << 20, want_match_count=False, want_total=True, want_anymatch=True, want_final=True,
-                 collect_stats=False, k_base=0, group_lanes=0, flags=0):
+                 collect_stats=False, k_base=0, group_lanes=0, flags=0, starts=False):
     """rx_match_ragged(): one-shot match of streams of different lengths (see ragged_batch for `data` / `offsets`).
     Returns the same dict as match(); anymatch rows span the longest stream's passes, zero past each stream's own."""
     data, offsets = ragged_batch(data, offsets)
     ns = offsets.size - 1
-    out = _Out(nfa, ns, _ragged_len(offsets), mode, events_cap, want_match_count, want_total, want_anymatch, want_final)
+    out = _Out(nfa, ns, _ragged_len(offsets), mode, events_cap, want_match_count, want_total, want_anymatch, want_final,
+               starts=starts)
     o = _mk_opts(device, mode, kernel, None, k_base, collect_stats, group_lanes, flags)
     ia = None
     if init_active is not None:
@@ -434,11 +446,11 @@ def match_ragged(nfa, data, offsets=None, mode=MODE_FULL, kernel=KERNEL_AUTO, de
 
 def match_sharded(nfa, data, devices, mode=MODE_FULL, kernel=KERNEL_AUTO, events_cap=1 << 20,
                   want_match_count=False, want_total=True, want_anymatch=True, want_final=True, collect_stats=False,
-                  group_lanes=0, flags=0):
+                  group_lanes=0, flags=0, starts=False):
     """rx_match_sharded(): contiguous stream blocks over several GPUs of this process, no collective."""
     data, stride = _as_rows(data)
     ns, sl = data.shape
-    out = _Out(nfa, ns, sl, mode, events_cap, want_match_count, want_total, want_anymatch, want_final)
+    out = _Out(nfa, ns, sl, mode, events_cap, want_match_count, want_total, want_anymatch, want_final, starts=starts)
     o = _mk_opts(-1, mode, kernel, None, 0, collect_stats, group_lanes, flags)
     devs = (C.c_int * len(devices))(*devices)
     _chk(lib().rx_match_sharded(nfa._h, data.ctypes.data, ns, sl, stride, devs, len(devices), C.byref(o),
@@ -523,13 +535,16 @@ class Plan:
              "rx_plan_kernel_times")
         return n.value, s.value, mn.value, mx.value
 
-    def download(self, want_total=True):
+    def download(self, want_total=True, starts=False):
+        """rx_plan_download(); starts=True: the match starts too (see match()), scanned from the launch's input, which must
+        still be the plan's."""
         wmc, wam, wfin = self.want
-        out = _Out(self.nfa, self.n_streams, self.stream_len, self.mode, self.events_cap, wmc, want_total, wam, wfin)
+        out = _Out(self.nfa, self.n_streams, self.stream_len, self.mode, self.events_cap, wmc, want_total, wam, wfin,
+                   starts=starts)
         _chk(lib().rx_plan_download(self._h, C.byref(out.r)), "rx_plan_download")
         return out.as_dict()
 
-    def run(self, data, want_total=True, register=True, compact_final=0):
+    def run(self, data, want_total=True, register=True, compact_final=0, starts=False):
         """rx_plan_run(): host rows in, host results out in one pipelined call (upload, kernel and download of blocks of
         streams overlap).  The output arrays live as long as the plan and are page-locked once (`register`), and so is
         `data` — pass the same array again and it moves by DMA.  Returns the same dict as download(); its arrays are
@@ -537,6 +552,9 @@ class Plan:
         + final_cnt[s]) per stream, at most N entries in all) instead of bitmask rows — a fraction of the bytes."""
         data, stride = _as_rows(data)
         ns, sl = data.shape
+        if starts:  # (rx_plan_run has no match starts: the library refuses them with RX_EINVAL)
+            o = _Out(self.nfa, ns, sl, self.mode, self.events_cap, False, False, False, False, starts=True)
+            _chk(lib().rx_plan_run(self._h, data.ctypes.data, ns, sl, stride, C.byref(o.r)), "rx_plan_run")
         key = (ns, sl, want_total, compact_final)
         if getattr(self, "_run_key", None) != key:
             self._release_run_buffers()
