@@ -348,6 +348,37 @@ int rx_plan_kernel_times(rx_plan* plan, uint32_t* n_launches, double* sum_ms, do
                          double* max_ms);
 /* Copy the last launch's results to the caller's arrays (sorted events, counts, ...). */
 int rx_plan_download(rx_plan* plan, rx_result* res);
+/* The last launch's results into the caller's DEVICE memory, in the canonical form rx_plan_download returns, without any host
+ * wait: everything is enqueued on the plan's stream behind the launch and the call returns at once (no stream
+ * synchronisation, no blocking copy, no allocation once the plan's scratch exists: it is grown on the first call, sized from
+ * the plan's events_cap and max_streams).  The outputs are ready when the plan's stream reaches this point (rx_plan_sync,
+ * an event, or later work on the same stream).  A gfx950 kernel puts the captured events into (stream, k, state) order — an
+ * LSD radix sort on the key (stream, k, state) that carries the match starts along — and builds the per-stream offsets; the
+ * other arrays are device-to-device copies.  Every output equals what rx_plan_download returns for the same launch, byte for
+ * byte, the truncation to events_cap and events_overflow included; rx_plan_download still works for the launch before or
+ * after this call.  Checks before anything is enqueued, as rx_plan_download: RX_ESTATE without a launch (or after
+ * rx_plan_run), for an output the plan was created without (want_match_count / want_anymatch / want_final), and for starts
+ * after new input or a new start set; RX_EINVAL for anymatch_stride below the pass count and for starts without events;
+ * RX_ECAPACITY for starts beyond the start kernel's LDS capacity.  In addition RX_EINVAL for an output pointer that is not
+ * device memory of the plan's device (host memory is refused), and RX_ECAPACITY when events are asked for and the sort key's
+ * bits — those of n_streams - 1, of the batch's largest pass count - 1 and of size - 1 — exceed 64 (no batch that fits in HBM
+ * does) or the plan's events_cap exceeds 2^31 (24 GB of events). */
+typedef struct rx_device_result {
+  uint32_t struct_size;      /* = sizeof(rx_device_result) */
+  uint32_t reserved0;
+  rx_event* events;          /* [events_cap]: sorted (stream, k, state), the first events_cap of those captured (NULL = none) */
+  size_t events_cap;
+  uint32_t* event_start;     /* [events_cap] or NULL: aligned with events, exactly as rx_result.event_start */
+  uint32_t* event_off;       /* [n_streams + 1] or NULL: stream s's events are events[event_off[s] .. event_off[s + 1]) */
+  uint64_t* info;            /* [4] or NULL: pulses (rx_stats.n_events), events returned (rx_result.n_events),
+                                events_overflow, streams handed off to RX_KERNEL_SYM_WAVE */
+  uint32_t* match_count;     /* as rx_result, device memory */
+  uint64_t* match_count_total;
+  uint32_t* anymatch;
+  size_t anymatch_stride;
+  uint64_t* final_active;
+} rx_device_result;
+int rx_plan_download_device(rx_plan* plan, rx_device_result* res);
 /* Host buffers in, host results out, in ONE call — the same results as rx_plan_upload + rx_plan_launch +
  * rx_plan_download, but pipelined: the batch is cut into up to 8 blocks of >= 32 768 streams that share three HIP
  * streams (uploads, kernels, downloads), so that the upload of block i+1, the kernel of block i and the download of

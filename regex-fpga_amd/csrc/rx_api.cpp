@@ -458,6 +458,11 @@ struct rx_plan {
   HipBuf<RxSlot> d_by_id;
   HipEvent st0, st1;
   bool start_input = false;
+  // rx_plan_download_device: sort scratch (two key / payload buffers of events_cap, per-block digit counts), starts in device
+  // order and descriptors by stream id of its own; grown on first use
+  HipBuf<unsigned long long> d_sort_key;
+  HipBuf<uint32_t> d_sort_val, d_sort_hist, d_dev_starts;
+  HipBuf<RxSlot> d_dev_by_id;
   size_t am_stride = 0;
   // current batch
   size_t n_streams = 0, stream_len = 0, stride = 0;
@@ -1660,6 +1665,117 @@ static int plan_download(rx_plan* p, rx_result* res) {
                      hipMemcpyDeviceToHost));
   }
   return RX_OK;
+}
+
+// ---- results into device memory ---------------------------------------------------------------------
+static uint32_t bit_width(uint64_t v) {
+  uint32_t b = 0;
+  while (v >> b) b++;
+  return b;
+}
+
+// a caller's output pointer: device memory of the plan's device (NULL = not wanted)
+static bool on_plan_device(const rx_plan* p, const void* ptr) {
+  if (!ptr) return true;
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+    (void)hipGetLastError();  // (plain host memory the runtime has never seen)
+    return false;
+  }
+  return at.type == hipMemoryTypeDevice && at.device == p->device;
+}
+
+extern "C" int rx_plan_download_device(rx_plan* p, rx_device_result* res) {
+  RX_TRY
+  if (!p || !res || res->struct_size < sizeof(rx_device_result)) return RX_EINVAL;
+  const bool want_starts = res->event_start != nullptr;
+  if (want_starts && (!res->events || !res->events_cap)) return RX_EINVAL;
+  if (!p->launched) return RX_ESTATE;
+  if (want_starts && !p->start_input) return RX_ESTATE;
+  if (want_starts && rx_start_capacity(p->nfa->h.size, p->tab.lds_per_cu)) return RX_ECAPACITY;
+  if ((res->match_count && !p->want_mc) || (res->anymatch && !p->want_am) || (res->final_active && !p->want_final))
+    return RX_ESTATE;
+  const RxHostNfa& h = p->nfa->h;
+  const RxParams& a = p->params;
+  const size_t am_need = (size_t)((a.n_passes + 31u) / 32u);
+  if (res->anymatch && res->anymatch_stride < am_need) return RX_EINVAL;
+  // the sort key: stream, pass and state of the batch side by side
+  const uint32_t sb = bit_width(p->n_streams - 1), kb = bit_width(a.n_passes ? a.n_passes - 1u : 0u), tb = bit_width(h.size - 1u);
+  const bool sort = res->events && res->events_cap && p->events_cap;
+  // (the sort kernels index and tile the count in 32 bits: 2^31 events keep every chunk end and tile step below 2^32)
+  if (sort && (sb + kb + tb > 64 || p->events_cap > (1ull << 31))) return RX_ECAPACITY;
+  int dev;
+  int rc = bind_device(p->device, &dev);
+  if (rc) return rc;
+  for (const void* q : {(const void*)res->events, (const void*)res->event_start, (const void*)res->event_off, (const void*)res->info,
+                        (const void*)res->match_count, (const void*)res->match_count_total, (const void*)res->anymatch,
+                        (const void*)res->final_active})
+    if (!on_plan_device(p, q)) return RX_EINVAL;
+  const size_t cap = p->events_cap;
+  const uint32_t grid = (uint32_t)std::min<size_t>(RX_SORT_BLOCKS_MAX, std::max<size_t>(1, (cap + 2047) / 2048));
+  if (sort && ((rc = p->d_sort_key.grow(2 * cap)) || (rc = p->d_sort_val.grow(2 * cap)) || (rc = p->d_sort_hist.grow(256u * grid))))
+    return rc;
+  RxSortArgs sa{};
+  sa.events = p->d_events.p;
+  sa.counters = p->d_counters;  // the set of the launch this call follows; the next launch zeroes it behind us on the stream
+  sa.plan_cap = (uint32_t)cap;
+  sa.stream_base = a.stream_base;
+  sa.k_base = a.k_base;
+  sa.k_bits = kb;
+  sa.state_bits = tb;
+  sa.n_passes = std::max<uint32_t>(1, (sb + kb + tb + 7) / 8);
+  sa.grid = grid;
+  sa.key[0] = p->d_sort_key.p;
+  sa.key[1] = p->d_sort_key.p ? p->d_sort_key.p + cap : nullptr;
+  sa.val[0] = p->d_sort_val.p;
+  sa.val[1] = p->d_sort_val.p ? p->d_sort_val.p + cap : nullptr;
+  sa.hist = p->d_sort_hist.p;
+  sa.out_events = res->events;
+  sa.out_cap = res->events ? res->events_cap : 0;
+  sa.out_start = res->event_start;
+  sa.out_off = res->event_off;
+  sa.n_streams = (uint32_t)p->n_streams;
+  sa.info = reinterpret_cast<unsigned long long*>(res->info);
+  sa.start_const = a.k_base;
+  if (want_starts && cap && (h.unanch_state != 0xFFFFFFFFu || h.state0_entered || a.init_active)) {
+    // (otherwise every start is k_base: plan_starts' shortcut)
+    DevTables t;
+    if ((rc = ensure_start_tables(p->nfa, p->device, &t)) || (rc = p->d_dev_starts.grow(cap))) return rc;
+    RxStartArgs st{};
+    st.events = p->d_events.p;
+    st.n_events = (uint32_t)cap;  // (the grid's size; the kernel reads the count)
+    st.start = p->d_dev_starts.p;
+    st.rev_off = t.rev_off;
+    st.rev = t.rev;
+    st.unanch = h.unanch_state;
+    if (p->ragged) {
+      if ((rc = p->d_dev_by_id.grow(p->max_streams))) return rc;
+      hipError_t e = (hipError_t)rx_launch_slots_by_id(p->d_slots.p, (uint32_t)p->n_streams, p->d_dev_by_id.p, p->stream);
+      if (e != hipSuccess) return hip_fail(e, "slot table launch");
+      st.by_id = p->d_dev_by_id.p;
+    }
+    hipError_t e = (hipError_t)rx_launch_starts(a, st, p->tab.cu_count, p->tab.lds_per_cu, p->stream, true);
+    if (e != hipSuccess) return hip_fail(e, "start kernel launch");
+    sa.starts_in = p->d_dev_starts.p;
+  }
+  hipError_t e = (hipError_t)rx_launch_device_results(sa, sort, p->stream);
+  if (e != hipSuccess) return hip_fail(e, "device result launch");
+  const size_t n = p->n_streams;
+  if (res->match_count)
+    HIPCHK(hipMemcpyAsync(res->match_count, p->d_mc.p, n * h.size * sizeof(uint32_t), hipMemcpyDeviceToDevice, p->stream));
+  if (res->match_count_total)
+    HIPCHK(hipMemcpyAsync(res->match_count_total, p->d_mct, (size_t)h.size * sizeof(uint64_t), hipMemcpyDeviceToDevice, p->stream));
+  if (res->anymatch && am_need) {
+    if (res->anymatch_stride == p->am_stride)
+      HIPCHK(hipMemcpyAsync(res->anymatch, p->d_am.p, n * p->am_stride * 4, hipMemcpyDeviceToDevice, p->stream));
+    else
+      HIPCHK(hipMemcpy2DAsync(res->anymatch, res->anymatch_stride * 4, p->d_am.p, p->am_stride * 4, am_need * 4, n,
+                              hipMemcpyDeviceToDevice, p->stream));
+  }
+  if (res->final_active)
+    HIPCHK(hipMemcpyAsync(res->final_active, p->d_final.p, n * a.nw64x2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, p->stream));
+  return RX_OK;
+  RX_CATCH
 }
 
 // ---- pipelined host-to-host run ---------------------------------------------------------------------

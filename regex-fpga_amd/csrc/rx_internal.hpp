@@ -187,6 +187,33 @@ struct RxStartArgs {
   uint32_t unanch;             // RxHostNfa::unanch_state
 };
 
+// The device-side download (rx_plan_download_device): the launch's captured events into (stream, k, state) order by an LSD
+// radix sort on a composite key, 8 bits per pass, with the event index as payload.  The count is read on the device:
+// captured = min(counters[0], plan_cap).  Key = ((stream - stream_base) << k_bits | (k - k_base)) << state_bits | state.
+// Each pass: per-block digit histograms, one scan, a stable scatter; the last pass writes the caller's arrays directly.
+static constexpr uint32_t RX_SORT_BLOCKS_MAX = 128;  // persistent grid: block b sorts the contiguous chunk b of the count
+struct RxSortArgs {
+  const rx_event* events;               // the launch's captured events, device order
+  const unsigned long long* counters;   // the launch's counter set: [0] pulses, [3] streams handed off
+  uint32_t plan_cap;                    // the plan's events_cap
+  uint32_t stream_base, k_base;
+  uint32_t k_bits, state_bits;
+  uint32_t n_passes;                    // >= 1
+  uint32_t grid;                        // blocks of every sort kernel
+  unsigned long long* key[2];           // [plan_cap] each: ping-pong between passes
+  uint32_t* val[2];
+  uint32_t* hist;                       // [grid][256]: a block's digit counts, then (scanned) its first position per digit
+  const uint32_t* starts_in;            // [plan_cap] start of every captured event, device order; null: start_const
+  uint32_t start_const;
+  // outputs (caller device memory; any may be null)
+  rx_event* out_events;
+  unsigned long long out_cap;
+  uint32_t* out_start;
+  uint32_t* out_off;                    // [n_streams + 1]
+  uint32_t n_streams;
+  unsigned long long* info;             // [4]
+};
+
 // rx_kernels.hip
 int rx_pick_launch(uint32_t kernel, uint32_t size, uint32_t n_streams, int cu_count, size_t lds_per_cu,
                    RxParams* p, RxLaunchCfg* cfg);
@@ -196,7 +223,14 @@ int rx_launch(const RxParams& p, const RxLaunchCfg& cfg, void* hip_stream);
 // ends as the number of entries the sets need, entries beyond `cap` are not written.
 // RX_ECAPACITY when one wavefront's bitmasks do not fit a CU's LDS (checked before anything is enqueued)
 int rx_start_capacity(uint32_t size, size_t lds_per_cu);
-int rx_launch_starts(const RxParams& p, const RxStartArgs& a, int cu_count, size_t lds_per_cu, void* hip_stream);
+// count_on_device: the build that reads the event count as min(p.counters[0], p.events_cap) on the device; a.n_events is then
+// the plan's events_cap (the grid's size)
+int rx_launch_starts(const RxParams& p, const RxStartArgs& a, int cu_count, size_t lds_per_cu, void* hip_stream,
+                     bool count_on_device = false);
+// by_id[slots[i].id] = slots[i] for i < n (the start kernel's ragged descriptors by stream id)
+int rx_launch_slots_by_id(const RxSlot* slots, uint32_t n, RxSlot* by_id, void* hip_stream);
+// The sort, its gather into the caller's arrays, event_off and info: everything after the start kernel
+int rx_launch_device_results(const RxSortArgs& a, bool sort, void* hip_stream);
 int rx_launch_final_compact(const uint32_t* rows, uint32_t n_streams, uint32_t row_words, uint32_t* states, uint32_t cap,
                             uint32_t* off, uint32_t* cnt, unsigned long long* counter, void* hip_stream);
 

@@ -2583,7 +2583,8 @@ __global__ void __launch_bounds__(1024) rx_final_compact_kernel(const uint32_t* 
 // The set is the wave kernels' list + bitmask pair (StreamState: exact dedup through ds_or on the bitmask, the dense form
 // beyond the list's capacity), so a start never depends on scheduling.  The byte classes of 256 bytes are loaded one chunk
 // ahead of the dependent chain (set -> predecessor gather -> dedup) and broadcast from a lane per step.
-template <bool RAGGED>
+// COUNT_ON_DEVICE (rx_plan_download_device): the event count is the launch's own, min(counters[0], events_cap), read here
+template <bool RAGGED, bool COUNT_ON_DEVICE = false>
 __global__ void __launch_bounds__(256) rx_start_kernel(const RxParams p, const RxStartArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -2608,7 +2609,9 @@ __global__ void __launch_bounds__(256) rx_start_kernel(const RxParams p, const R
     return r;
   };
 
-  for (uint32_t i = blockIdx.x * wpb + wib; i < a.n_events; i += gridDim.x * wpb) {
+  uint32_t n_events = a.n_events;
+  if constexpr (COUNT_ON_DEVICE) n_events = (uint32_t)min(p.counters[0], (unsigned long long)p.events_cap);
+  for (uint32_t i = blockIdx.x * wpb + wib; i < n_events; i += gridDim.x * wpb) {
     const rx_event ev = a.events[i];
     const uint32_t id = ev.stream - p.stream_base, k = ev.k - p.k_base;
     std::conditional_t<RAGGED, RaggedFeed, ByteFeed> feed;
@@ -2686,6 +2689,160 @@ __global__ void __launch_bounds__(256) rx_start_kernel(const RxParams p, const R
   }
 }
 
+
+// =================================================================================================
+// Device-side download (rx_plan_download_device): captured events -> (stream, k, state) order on the device
+// =================================================================================================
+// An LSD radix sort, 8 bits per pass, of the composite key of RxSortArgs with the event index as payload.  The count is only
+// known on the device, so every kernel runs a fixed grid and block b takes the contiguous chunk b of it: per-block histograms
+// in block order then give a stable scatter.  Pass 0 builds the keys from the events; the last pass writes the caller's events
+// (and starts) at their final positions, truncated to the caller's capacity.
+__device__ __forceinline__ uint32_t sort_captured(const RxSortArgs& a) {
+  return (uint32_t)min(a.counters[0], (unsigned long long)a.plan_cap);
+}
+__device__ __forceinline__ unsigned long long sort_key(const RxSortArgs& a, const rx_event& e) {
+  unsigned long long key = e.stream - a.stream_base;
+  key = (key << a.k_bits) | (e.k - a.k_base);
+  return (key << a.state_bits) | e.state;
+}
+// block b's chunk [*lo, *hi) of the n captured events
+__device__ __forceinline__ void sort_chunk(const RxSortArgs& a, uint32_t n, uint32_t* lo, uint32_t* hi) {
+  const uint32_t per = (n + a.grid - 1u) / a.grid;
+  *lo = min(n, blockIdx.x * per);
+  *hi = min(n, *lo + per);
+}
+__device__ __forceinline__ void sort_load(const RxSortArgs& a, uint32_t pass, uint32_t i, unsigned long long* key, uint32_t* val) {
+  if (pass == 0) {
+    *key = sort_key(a, a.events[i]);
+    *val = i;
+  } else {
+    *key = a.key[(pass - 1u) & 1u][i];
+    *val = a.val[(pass - 1u) & 1u][i];
+  }
+}
+
+__global__ void __launch_bounds__(256) rx_sort_hist_kernel(const RxSortArgs a, uint32_t pass) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0u;
+  __syncthreads();
+  uint32_t lo, hi;
+  sort_chunk(a, sort_captured(a), &lo, &hi);
+  for (uint32_t i = lo + threadIdx.x; i < hi; i += 256u) {
+    unsigned long long key;
+    uint32_t val;
+    sort_load(a, pass, i, &key, &val);
+    atomicAdd(&h[(uint32_t)(key >> (8u * pass)) & 255u], 1u);
+  }
+  __syncthreads();
+  a.hist[blockIdx.x * 256u + threadIdx.x] = h[threadIdx.x];
+}
+
+// One block: hist[b][d] := the first position of digit d in block b's share (digits ascending, blocks in order within one)
+__global__ void __launch_bounds__(256) rx_sort_scan_kernel(const RxSortArgs a) {
+  __shared__ uint32_t wsum[4];
+  const uint32_t d = threadIdx.x, lane = d & 63u, w = d >> 6;
+  uint32_t tot = 0;
+  for (uint32_t b = 0; b < a.grid; b++) tot += a.hist[b * 256u + d];
+  uint32_t incl = tot;  // exclusive scan of the digit totals over the block
+  for (int s = 1; s < 64; s <<= 1) {
+    const uint32_t v = (uint32_t)__shfl_up((int)incl, s);
+    if (lane >= (uint32_t)s) incl += v;
+  }
+  if (lane == 63u) wsum[w] = incl;
+  __syncthreads();
+  uint32_t run = incl - tot;
+  for (uint32_t q = 0; q < w; q++) run += wsum[q];
+  for (uint32_t b = 0; b < a.grid; b++) {
+    const uint32_t c = a.hist[b * 256u + d];
+    a.hist[b * 256u + d] = run;
+    run += c;
+  }
+}
+
+// Stable scatter: tiles of 256 in order; within a wavefront the rank among the lanes with the same digit comes from eight
+// ballots, across the block's four wavefronts from per-wave counters, across tiles from the running position per digit.
+__global__ void __launch_bounds__(256) rx_sort_scatter_kernel(const RxSortArgs a, uint32_t pass) {
+  __shared__ uint32_t run[256];
+  __shared__ uint32_t wcnt[4][256];
+  const uint32_t t = threadIdx.x, w = t >> 6;
+  const bool last = pass + 1u == a.n_passes;
+  run[t] = a.hist[blockIdx.x * 256u + t];
+  uint32_t lo, hi;
+  sort_chunk(a, sort_captured(a), &lo, &hi);
+  for (uint32_t base = lo; base < hi; base += 256u) {
+    for (uint32_t q = 0; q < 4u; q++) wcnt[q][t] = 0u;
+    const uint32_t i = base + t;
+    const bool valid = i < hi;
+    unsigned long long key = 0;
+    uint32_t val = 0;
+    if (valid) sort_load(a, pass, i, &key, &val);
+    const uint32_t dig = (uint32_t)(key >> (8u * pass)) & 255u;
+    uint64_t same = wballot(valid);
+#pragma unroll
+    for (uint32_t bit = 0; bit < 8u; bit++) {
+      const uint64_t m = wballot((dig >> bit) & 1u);
+      same &= ((dig >> bit) & 1u) ? m : ~m;
+    }
+    const uint32_t rank = rank_below(same);
+    __syncthreads();  // (wcnt zeroed; the previous tile's positions read)
+    if (valid && rank == 0u) wcnt[w][dig] = (uint32_t)__popcll(same);
+    __syncthreads();
+    {
+      uint32_t r = run[t];
+      for (uint32_t q = 0; q < 4u; q++) {
+        const uint32_t c = wcnt[q][t];
+        wcnt[q][t] = r;
+        r += c;
+      }
+      run[t] = r;
+    }
+    __syncthreads();
+    if (valid) {
+      const uint32_t pos = wcnt[w][dig] + rank;
+      if (!last) {
+        a.key[pass & 1u][pos] = key;
+        a.val[pass & 1u][pos] = val;
+      } else if (pos < a.out_cap) {
+        a.out_events[pos] = a.events[val];
+        if (a.out_start) a.out_start[pos] = a.starts_in ? a.starts_in[val] : a.start_const;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// event_off[s] = the first returned event of a stream >= s (binary search over the sorted events), and info[0..3]
+__global__ void __launch_bounds__(256) rx_sort_finish_kernel(const RxSortArgs a) {
+  const unsigned long long pulses = a.counters[0];
+  const uint32_t captured = sort_captured(a);
+  const bool have = a.out_events && a.out_cap && captured;
+  const uint32_t n = have ? (uint32_t)min((unsigned long long)captured, a.out_cap) : 0u;
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (a.out_off && s <= a.n_streams) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (a.out_events[mid].stream - a.stream_base < s) lo = mid + 1u; else hi = mid;
+    }
+    a.out_off[s] = lo;
+  }
+  if (a.info && s == 0u) {
+    // events_overflow exactly as rx_plan_download sets it
+    uint32_t ovf = pulses > a.plan_cap ? 1u : 0u;
+    if (have && captured > a.out_cap) ovf = 1u;
+    else if (!have && pulses && (!a.out_events || !a.out_cap)) ovf = a.out_events ? 1u : 0u;
+    a.info[0] = pulses;
+    a.info[1] = n;
+    a.info[2] = ovf;
+    a.info[3] = a.counters[3];
+  }
+}
+
+__global__ void __launch_bounds__(256) rx_slots_by_id_kernel(const RxSlot* __restrict__ slots, uint32_t n, RxSlot* __restrict__ by_id) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n) by_id[slots[i].id] = slots[i];
+}
+
 }  // namespace
 
 int rx_launch_final_compact(const uint32_t* rows, uint32_t n_streams, uint32_t row_words, uint32_t* states, uint32_t cap,
@@ -2704,7 +2861,8 @@ int rx_start_capacity(uint32_t size, size_t lds_per_cu) {
   return (2u * nw32 + 2u * RX_LIST_CAP) * 4u <= lds_per_cu ? RX_OK : RX_ECAPACITY;
 }
 
-int rx_launch_starts(const RxParams& launched, const RxStartArgs& a, int cu_count, size_t lds_per_cu, void* hip_stream) {
+int rx_launch_starts(const RxParams& launched, const RxStartArgs& a, int cu_count, size_t lds_per_cu, void* hip_stream,
+                     bool count_on_device) {
   if (a.n_events == 0) return 0;
   RxParams p = launched;  // the launch's batch (bytes, slots, start rows, k_base); the carve is the start kernel's own
   const uint32_t nw32 = (p.size + 31u) / 32u;
@@ -2726,7 +2884,32 @@ int rx_launch_starts(const RxParams& launched, const RxStartArgs& a, int cu_coun
     hipLaunchKernelGGL(kern, dim3(grid), dim3(wpb * 64u), lds, s, p, a);
     return (int)hipGetLastError();
   };
+  if (count_on_device) return p.slots ? go(rx_start_kernel<true, true>) : go(rx_start_kernel<false, true>);
   return p.slots ? go(rx_start_kernel<true>) : go(rx_start_kernel<false>);
+}
+
+// ---- device-side download -------------------------------------------------------------------------
+int rx_launch_slots_by_id(const RxSlot* slots, uint32_t n, RxSlot* by_id, void* hip_stream) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(rx_slots_by_id_kernel, dim3((n + 255u) / 256u), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), slots,
+                     n, by_id);
+  return (int)hipGetLastError();
+}
+
+int rx_launch_device_results(const RxSortArgs& a, bool sort, void* hip_stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  hipError_t e;
+  for (uint32_t pass = 0; sort && pass < a.n_passes; pass++) {
+    hipLaunchKernelGGL(rx_sort_hist_kernel, dim3(a.grid), dim3(256), 0, s, a, pass);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(rx_sort_scan_kernel, dim3(1), dim3(256), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(rx_sort_scatter_kernel, dim3(a.grid), dim3(256), 0, s, a, pass);
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+  }
+  const uint32_t blocks = a.out_off ? a.n_streams / 256u + 1u : 1u;  // n_streams + 1 offsets
+  hipLaunchKernelGGL(rx_sort_finish_kernel, dim3(blocks), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
 }
 
 // -------------------------------------------------------------------------------------------------

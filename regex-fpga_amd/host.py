@@ -55,6 +55,13 @@ class _Result(C.Structure):
                 ("final_states_cap", C.c_size_t), ("n_final_states", C.c_size_t), ("final_states_overflow", C.c_uint32),
                 ("reserved0", C.c_uint32), ("event_start", C.c_void_p), ("start_ms", C.c_double)]
 
+class _DeviceResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32), ("events", C.c_void_p), ("events_cap", C.c_size_t),
+                ("event_start", C.c_void_p), ("event_off", C.c_void_p), ("info", C.c_void_p), ("match_count", C.c_void_p),
+                ("match_count_total", C.c_void_p), ("anymatch", C.c_void_p), ("anymatch_stride", C.c_size_t),
+                ("final_active", C.c_void_p)]
+
+
 # rx_result.event_start: the match began before the batch (a chained stream's earlier part); see include/rxmatch.h
 START_BEFORE = 0xFFFFFFFF
 
@@ -72,7 +79,8 @@ ABI_SYMBOLS = ["rx_nfa_dfa_info", "rx_nfa_dfa_reset", "rx_compile_patterns", "rx
                "rx_match_sharded", "rx_plan_create", "rx_plan_upload", "rx_plan_set_device_input",
                "rx_plan_set_init_active", "rx_plan_launch", "rx_plan_sync", "rx_plan_kernel_times", "rx_plan_download", "rx_plan_free",
                "rx_device_count", "rx_device_name", "rx_plan_run", "rx_host_register", "rx_host_unregister", "rx_plan_tune",
-               "rx_plan_busy", "rx_match_ragged", "rx_plan_upload_ragged", "rx_plan_set_device_input_ragged"]
+               "rx_plan_busy", "rx_match_ragged", "rx_plan_upload_ragged", "rx_plan_set_device_input_ragged",
+               "rx_plan_download_device"]
 
 _lib = None
 
@@ -152,6 +160,8 @@ def lib():
                                        C.POINTER(C.c_double)]
     L.rx_plan_download.argtypes = [vp, C.POINTER(_Result)]
     L.rx_plan_run.argtypes = [vp, vp, sz, sz, sz, C.POINTER(_Result)]
+    if hasattr(L, "rx_plan_download_device"):  # (likewise)
+        L.rx_plan_download_device.argtypes = [vp, C.POINTER(_DeviceResult)]
     L.rx_host_register.argtypes = [vp, sz]
     L.rx_host_unregister.argtypes = [vp]
     L.rx_plan_free.argtypes = [vp]
@@ -458,6 +468,56 @@ def match_sharded(nfa, data, devices, mode=MODE_FULL, kernel=KERNEL_AUTO, events
     return out.as_dict()
 
 
+def device_result_arrays(out, dev, n_streams, size, nw64, nw, cap, starts, want_total, want_mc, want_am, want_final):
+    """The torch tensors Plan.download_device writes for a batch of n_streams streams (nw any-match words per row, events_cap
+    `cap`), and the events cap to pass: new ones (out None), or those of `out` after checking that each one the call writes
+    is there and holds the batch — on `dev`, of its dtype, and large enough for every byte the library writes through its
+    pointer.  ValueError otherwise: the library takes bare pointers and would write past the end of a smaller tensor."""
+    import torch
+    i32, i64 = torch.int32, torch.int64
+    if out is None:
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        am_stride = (nw + 7) & ~7
+        return dict(events=e((max(cap, 1), 3), i32), start=e(max(cap, 1), i32) if starts else None,
+                    event_off=e(n_streams + 1, i32), info=e(4, i64),
+                    match_count=e((n_streams, size), i32) if want_mc else None,
+                    match_count_total=e(size, i64) if want_total else None,
+                    anymatch=e((n_streams, am_stride), i32) if want_am else None,
+                    final_active=e((n_streams, nw64), i64) if want_final else None), cap
+
+    def take(key, dtype, rows, row_len=None, strided=False):
+        t = out.get(key)
+        if t is None:
+            raise ValueError(f"download_device(out=...): out has no '{key}' tensor, and this call writes one")
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype:
+            raise ValueError(f"download_device(out=...): out['{key}'] must be a {dtype} tensor on {dev}")
+        if row_len is None:  # flat: `rows` elements from data_ptr on
+            if not t.is_contiguous() or t.numel() < rows:
+                raise ValueError(f"download_device(out=...): out['{key}'] must be contiguous with >= {rows} elements, "
+                                 f"has {t.numel()}")
+        elif strided:  # rows of row_len elements, stride(0) apart, up to rows * stride(0) elements (the flat copy's extent)
+            ok = (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= row_len and t.shape[0] >= rows and
+                  t.storage_offset() + rows * t.stride(0) <= t.untyped_storage().nbytes() // t.element_size())
+            if not ok:
+                raise ValueError(f"download_device(out=...): out['{key}'] must have >= {rows} rows of >= {row_len} elements")
+        elif not (t.is_contiguous() and t.dim() == 2 and t.shape[1] == row_len and t.shape[0] >= rows):
+            raise ValueError(f"download_device(out=...): out['{key}'] must be contiguous [>= {rows}, {row_len}], "
+                             f"is {list(t.shape)}")
+        return t
+
+    for key, wanted in (("start", starts), ("match_count_total", want_total)):
+        if (out.get(key) is not None) != bool(wanted):
+            raise ValueError(f"download_device(out=...): out {'lacks' if wanted else 'has'} a '{key}' tensor, and this call "
+                             f"{'writes' if wanted else 'does not write'} one")
+    ev = take("events", i32, 1, 3)
+    cap = min(cap, ev.shape[0])
+    return dict(events=ev, start=take("start", i32, cap) if starts else None, event_off=take("event_off", i32, n_streams + 1),
+                info=take("info", i64, 4), match_count=take("match_count", i32, n_streams, size) if want_mc else None,
+                match_count_total=take("match_count_total", i64, size) if want_total else None,
+                anymatch=take("anymatch", i32, n_streams, nw, strided=True) if want_am else None,
+                final_active=take("final_active", i64, n_streams, nw64) if want_final else None), cap
+
+
 class Plan:
     """rx_plan: inputs stay resident in HBM across launches (serving / benchmarking)."""
 
@@ -472,6 +532,11 @@ class Plan:
         _chk(lib().rx_plan_create(nfa._h, C.byref(self._o), max_streams, max_stream_len, events_cap,
                                   int(want_match_count), int(want_anymatch), int(want_final), C.byref(self._h)),
              "rx_plan_create")
+        self.device = device
+        if device < 0:  # the device rx_plan_create bound: the calling thread's current HIP device, now
+            d = C.c_int(-1)
+            if lib().hipGetDevice(C.byref(d)) == 0:
+                self.device = d.value
         self.n_streams = self.stream_len = 0
         self._keep = None
 
@@ -543,6 +608,49 @@ class Plan:
                    starts=starts)
         _chk(lib().rx_plan_download(self._h, C.byref(out.r)), "rx_plan_download")
         return out.as_dict()
+
+    def download_device(self, starts=False, want_total=True, events_cap=None, out=None):
+        """rx_plan_download_device(): the same results as download(), as torch tensors on the plan's device, enqueued on the
+        plan's stream without any host wait.  Returns download()'s keys plus `event_off` (int32 [n_streams + 1]) and `info`
+        (int64 [4]: pulses, events returned, events_overflow, streams handed off).  Values that only the device knows stay
+        tensors: `events` (int32 [events_cap, 3]: stream, k, state) and `start` (int32 [events_cap]) hold info[1] valid rows,
+        `n_events` is info[0] and `events_overflow` info[2]; `stats` is None.  Unsigned values come as the signed torch
+        type of their width (view the bits, e.g. `.cpu().numpy().view(np.uint32)`).  `out`: a dict an earlier call returned,
+        refilled in place; every tensor the call writes must be there and hold the current batch (device_result_arrays),
+        else ValueError before anything is enqueued.  Torch's current stream waits for the plan's stream (and the plan's
+        stream for it, so that the tensors' memory is free to write): the results can be used there at once."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        cap = self.events_cap if events_cap is None else int(events_cap)
+        nw = max((n_passes(self.stream_len, self.mode) + 31) // 32, 1)
+        wmc, wam, wfin = self.want
+        a, cap = device_result_arrays(out, dev, self.n_streams, self.nfa.size, self.nfa.nw64, nw, cap, starts, want_total,
+                                      wmc, wam, wfin)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        o = _DeviceResult()
+        o.struct_size = C.sizeof(_DeviceResult)
+        if cap:  # (no events wanted: NULL, as download() passes it)
+            o.events, o.events_cap = ptr(a["events"]), cap
+        o.event_start, o.event_off, o.info = ptr(a["start"]), ptr(a["event_off"]), ptr(a["info"])
+        o.match_count, o.match_count_total = ptr(a["match_count"]), ptr(a["match_count_total"])
+        if a["anymatch"] is not None:
+            o.anymatch, o.anymatch_stride = ptr(a["anymatch"]), a["anymatch"].stride(0)
+        o.final_active = ptr(a["final_active"])
+        cur = torch.cuda.current_stream(dev)
+        mine = torch.cuda.ExternalStream(self._o.stream, device=dev) if self._o.stream else torch.cuda.default_stream(dev)
+        same = cur.cuda_stream == mine.cuda_stream
+        if not same:
+            mine.wait_stream(cur)  # (torch may hand out memory that work queued on its stream still uses)
+        _chk(lib().rx_plan_download_device(self._h, C.byref(o)), "rx_plan_download_device")
+        if not same:
+            cur.wait_stream(mine)
+        ns = self.n_streams
+        cut = lambda t, *idx: t[idx] if t is not None else None  # noqa: E731
+        return dict(events=a["events"], start=a["start"], event_off=a["event_off"][:ns + 1], info=a["info"][:4],
+                    n_events=a["info"][0], events_overflow=a["info"][2], match_count=cut(a["match_count"], slice(0, ns)),
+                    match_count_total=cut(a["match_count_total"], slice(0, self.nfa.size)),
+                    anymatch=cut(a["anymatch"], slice(0, ns), slice(0, nw)), final_active=cut(a["final_active"], slice(0, ns)),
+                    final_states=None, final_off=None, final_cnt=None, final_states_overflow=False, stats=None)
 
     def run(self, data, want_total=True, register=True, compact_final=0, starts=False):
         """rx_plan_run(): host rows in, host results out in one pipelined call (upload, kernel and download of blocks of
