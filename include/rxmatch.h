@@ -235,15 +235,17 @@ typedef struct rx_result {
                                 set iff some accept state was active in pass k            */
   size_t anymatch_stride;    /* in u32 words, >= ceil(n_passes/32); a multiple of 8 that equals
                                 ceil(ceil(max passes / 32) / 8) * 8 of the plan is copied flat,
-                                any other pitch row by row                                 */
+                                any other pitch row by row.  Words [ceil(n_passes/32), stride)
+                                of a row are unspecified after a flat copy and left untouched
+                                by a row-by-row one                                        */
   uint64_t* final_active;    /* [n_streams][ceil(size/64)]: S after the last pass's byte  */
   rx_stats stats;            /* out */
   /* The same final sets as compact lists (the plan must have been created with want_final): the states of
    * stream s are final_states[final_off[s] .. final_off[s] + final_cnt[s]), ascending.  The bitmask rows are 1.2 KB per
    * stream for snort_16 whatever they hold — 90 % of what a call downloads; the lists are ~12 bytes + 4 per active state.
-   * All three arrays or none; final_active may be NULL then.  rx_plan_run and rx_match from reset; rx_match with a start
-   * set, rx_match_sharded and rx_plan_download return RX_EINVAL / ignore them.  A caller whose struct_size ends before
-   * these fields gets rows. */
+   * All three arrays or none; final_active may be NULL then (given too, it gets the rows as well).  rx_plan_run and
+   * rx_match from reset; rx_match with a start set, rx_match_sharded and rx_plan_download return RX_EINVAL / ignore them.
+   * A caller whose struct_size ends before these fields gets rows. */
   uint32_t* final_states;    /* [final_states_cap] */
   uint32_t* final_off;       /* [n_streams] */
   uint32_t* final_cnt;       /* [n_streams] */

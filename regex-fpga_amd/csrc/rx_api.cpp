@@ -1936,8 +1936,9 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
     HIPCHK(hipStreamWaitEvent(p->s_k, q.up.e, 0));
     HIPCHK(hipEventRecord(q.k0.e, p->s_k));
     // compact final sets: the pack kernel (and the wave kernel behind it) writes the lists itself and builds no rows; the
-    // other kernels leave rows, which a small kernel behind them turns into lists
-    const bool direct = compact && cfg.kernel == RX_KERNEL_SYM_PACK;
+    // other kernels leave rows, which a small kernel behind them turns into lists.  A caller that wants the rows as well
+    // gets that second form from every kernel.
+    const bool direct = compact && !res->final_active && cfg.kernel == RX_KERNEL_SYM_PACK;
     if (direct) {
       a.fin_states = p->d_fstates.p;
       a.fin_cap = (uint32_t)res->final_states_cap;
@@ -2016,7 +2017,8 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   const unsigned long long* ev_after = p->h_run_ctr.p + 2;  // accept events of blocks 0..b
   const unsigned long long ev_total = p->h_run_ctr.p[0];
   st.n_events = ev_total;
-  if (ev_total > p->events_cap && res->events) res->events_overflow = 1u;
+  // (as rx_plan_download: the caller's capacity counts too, 0 included)
+  if (res->events && ev_total > std::min<unsigned long long>(p->events_cap, res->events_cap)) res->events_overflow = 1u;
   const size_t captured = (size_t)std::min<unsigned long long>(ev_total, p->events_cap);
   // The two downloads whose sizes the host has only now: both go out together, into page-locked staging (a blocking copy
   // into the caller's pageable arrays, one after the other, was 0.3 of the 2.5 ms of a configs[2] call); the events are put
@@ -2270,6 +2272,8 @@ extern "C" int rx_match_sharded(const rx_nfa* nfa, const uint8_t* bytes, size_t 
     res->stats.n_launches += x.r.stats.n_launches;
     res->stats.tb_cycles += x.r.stats.tb_cycles;  // pairs never straddle shards when every shard is even-sized
   }
+  // (the shards got no events array when events_cap is 0: they cannot report the overflow themselves)
+  if (res->events && res->stats.n_events > res->n_events) res->events_overflow = 1;
   return RX_OK;
   RX_CATCH
 }

@@ -474,8 +474,9 @@ def test_lazy_dfa_cache_is_persistent_and_resettable(rx, orx, automata, traces):
 
 def test_pipelined_host_to_host_run(rx, orx, automata, traces, gpu_nfas):
     """rx_plan_run (blocks of streams pipelined over HIP streams, page-locked caller buffers) == upload + launch +
-    download == the oracle: several blocks with events on both sides of every block boundary, one block, ragged length,
-    statistics and per-stream counters, repeated runs on one plan with the same and with a new input array."""
+    download == the oracle: one block of 40 000 or 33 000 streams (fewer than two blocks' worth), smaller batches, ragged
+    length, statistics and per-stream counters, repeated runs on one plan with the same and with a new input array.
+    Batches of several blocks are compared with the oracle in test_gpu_outputs.py."""
     W, size = automata["snort_16"]
     wl = rx.workloads
     lo, hi = traces[("snort_16", "lo")], traces[("snort_16", "hi")]
