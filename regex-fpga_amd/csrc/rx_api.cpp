@@ -1544,7 +1544,8 @@ static int plan_starts(rx_plan* p, size_t n, uint32_t* starts, double* ms) {
   }
   if (!p->st0.e && ((rc = p->st0.create()) || (rc = p->st1.create()))) return rc;
   HIPCHK(hipEventRecord(p->st0.e, p->stream));
-  const hipError_t e = (hipError_t)rx_launch_starts(a, sa, p->tab.cu_count, p->tab.lds_per_cu, p->stream);
+  const hipError_t e = (hipError_t)rx_launch_starts(a, sa, p->tab.cu_count, p->tab.lds_per_cu, p->stream, false,
+                                                    (p->opts.flags & RX_OPT_VERBOSE) != 0);
   if (e != hipSuccess) return hip_fail(e, "start kernel launch");
   HIPCHK(hipEventRecord(p->st1.e, p->stream));
   HIPCHK(hipMemcpyAsync(starts, p->d_starts.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream));
@@ -1689,6 +1690,7 @@ extern "C" int rx_plan_download_device(rx_plan* p, rx_device_result* res) {
   RX_TRY
   if (!p || !res || res->struct_size < sizeof(rx_device_result)) return RX_EINVAL;
   const bool want_starts = res->event_start != nullptr;
+  const bool verbose = (p->opts.flags & RX_OPT_VERBOSE) != 0;
   if (want_starts && (!res->events || !res->events_cap)) return RX_EINVAL;
   if (!p->launched) return RX_ESTATE;
   if (want_starts && !p->start_input) return RX_ESTATE;
@@ -1750,15 +1752,15 @@ extern "C" int rx_plan_download_device(rx_plan* p, rx_device_result* res) {
     st.unanch = h.unanch_state;
     if (p->ragged) {
       if ((rc = p->d_dev_by_id.grow(p->max_streams))) return rc;
-      hipError_t e = (hipError_t)rx_launch_slots_by_id(p->d_slots.p, (uint32_t)p->n_streams, p->d_dev_by_id.p, p->stream);
+      hipError_t e = (hipError_t)rx_launch_slots_by_id(p->d_slots.p, (uint32_t)p->n_streams, p->d_dev_by_id.p, p->stream, verbose);
       if (e != hipSuccess) return hip_fail(e, "slot table launch");
       st.by_id = p->d_dev_by_id.p;
     }
-    hipError_t e = (hipError_t)rx_launch_starts(a, st, p->tab.cu_count, p->tab.lds_per_cu, p->stream, true);
+    hipError_t e = (hipError_t)rx_launch_starts(a, st, p->tab.cu_count, p->tab.lds_per_cu, p->stream, true, verbose);
     if (e != hipSuccess) return hip_fail(e, "start kernel launch");
     sa.starts_in = p->d_dev_starts.p;
   }
-  hipError_t e = (hipError_t)rx_launch_device_results(sa, sort, p->stream);
+  hipError_t e = (hipError_t)rx_launch_device_results(sa, sort, p->stream, verbose);
   if (e != hipSuccess) return hip_fail(e, "device result launch");
   const size_t n = p->n_streams;
   if (res->match_count)
@@ -1844,6 +1846,7 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   if (n_streams == 0 || n_streams > p->max_streams || stream_len > p->max_len || stride < stream_len) return RX_EINVAL;
   if ((res->match_count && !p->want_mc) || (res->anymatch && !p->want_am) || (res->final_active && !p->want_final)) return RX_ESTATE;
   const bool compact = res->final_states || res->final_off || res->final_cnt;
+  const bool verbose = (p->opts.flags & RX_OPT_VERBOSE) != 0;
   if (compact) {
     if (!res->final_states || !res->final_off || !res->final_cnt || res->final_states_cap == 0) return RX_EINVAL;
     if (!p->want_final) return RX_ESTATE;
@@ -1950,7 +1953,7 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     if (compact && !direct) {  // the lists of all blocks share the caller's capacity; offsets are positions in the whole buffer
       e = (hipError_t)rx_launch_final_compact(a.final_active, a.n_streams, a.nw64x2, p->d_fstates.p, (uint32_t)res->final_states_cap,
-                                              p->d_foff.p + s0, p->d_fcnt.p + s0, d_run_ctr + 1, p->s_k);
+                                              p->d_foff.p + s0, p->d_fcnt.p + s0, d_run_ctr + 1, p->s_k, verbose);
       if (e != hipSuccess) return hip_fail(e, "final-set compaction launch");
     }
     HIPCHK(hipMemcpyAsync(d_run_ctr + 2 + b, d_run_ctr, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->s_k));
@@ -1985,7 +1988,6 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
   }
   // the counters and their per-block snapshots (the last block's k1 orders this copy behind every kernel)
   HIPCHK(hipMemcpyAsync(p->h_run_ctr.p, d_run_ctr, (2 + 2 * MAX_BLOCKS) * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->s_out));
-  const bool verbose = (p->opts.flags & RX_OPT_VERBOSE) != 0;
   const auto w_issued = std::chrono::steady_clock::now();
   HIPCHK(hipStreamSynchronize(p->s_out));
   if (verbose)
@@ -2014,6 +2016,8 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
     if (res->match_count_total)
       for (uint32_t i = 0; i < size; i++) res->match_count_total[i] += cnt[16 + i];
   }
+  if (verbose && spilled)  // (as plan_download)
+    fprintf(stderr, "[rxmatch] %llu of %zu streams were handed to the wave kernel\n", spilled, n_streams);
   const unsigned long long* ev_after = p->h_run_ctr.p + 2;  // accept events of blocks 0..b
   const unsigned long long ev_total = p->h_run_ctr.p[0];
   st.n_events = ev_total;

@@ -225,14 +225,15 @@ int rx_launch(const RxParams& p, const RxLaunchCfg& cfg, void* hip_stream);
 int rx_start_capacity(uint32_t size, size_t lds_per_cu);
 // count_on_device: the build that reads the event count as min(p.counters[0], p.events_cap) on the device; a.n_events is then
 // the plan's events_cap (the grid's size)
+// verbose (rx_opts.flags & RX_OPT_VERBOSE), here and in the launchers below: one stderr line per launch naming the kernel
 int rx_launch_starts(const RxParams& p, const RxStartArgs& a, int cu_count, size_t lds_per_cu, void* hip_stream,
-                     bool count_on_device = false);
+                     bool count_on_device, bool verbose);
 // by_id[slots[i].id] = slots[i] for i < n (the start kernel's ragged descriptors by stream id)
-int rx_launch_slots_by_id(const RxSlot* slots, uint32_t n, RxSlot* by_id, void* hip_stream);
+int rx_launch_slots_by_id(const RxSlot* slots, uint32_t n, RxSlot* by_id, void* hip_stream, bool verbose);
 // The sort, its gather into the caller's arrays, event_off and info: everything after the start kernel
-int rx_launch_device_results(const RxSortArgs& a, bool sort, void* hip_stream);
+int rx_launch_device_results(const RxSortArgs& a, bool sort, void* hip_stream, bool verbose);
 int rx_launch_final_compact(const uint32_t* rows, uint32_t n_streams, uint32_t row_words, uint32_t* states, uint32_t cap,
-                            uint32_t* off, uint32_t* cnt, unsigned long long* counter, void* hip_stream);
+                            uint32_t* off, uint32_t* cnt, unsigned long long* counter, void* hip_stream, bool verbose);
 
 // ---- host-side automaton (rx_host.cpp; no HIP in here) ---------------------------------------
 struct RxHostNfa {

@@ -2845,10 +2845,23 @@ __global__ void __launch_bounds__(256) rx_slots_by_id_kernel(const RxSlot* __res
 
 }  // namespace
 
+// RX_OPT_VERBOSE: the launched kernel's symbol (the mangled name it was registered with; what tests match against the
+// code object's kernel list)
+static const char* kernel_name(const void* kern, hipStream_t s) {
+  const char* n = hipKernelNameRefByPtr(kern, s);
+  return n ? n : "?";
+}
+
+static void log_launch(const void* kern, hipStream_t s, uint32_t grid, uint32_t block, uint32_t lds) {
+  fprintf(stderr, "[rxmatch] launch %s grid %u x %u threads, %u B LDS/block\n", kernel_name(kern, s), grid, block, lds);
+}
+
 int rx_launch_final_compact(const uint32_t* rows, uint32_t n_streams, uint32_t row_words, uint32_t* states, uint32_t cap,
-                            uint32_t* off, uint32_t* cnt, unsigned long long* counter, void* hip_stream) {
+                            uint32_t* off, uint32_t* cnt, unsigned long long* counter, void* hip_stream, bool verbose) {
   if (n_streams == 0) return 0;
-  hipLaunchKernelGGL(rx_final_compact_kernel, dim3((n_streams + 15u) / 16u), dim3(1024), 0, reinterpret_cast<hipStream_t>(hip_stream), rows,
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  if (verbose) log_launch(reinterpret_cast<const void*>(rx_final_compact_kernel), s, (n_streams + 15u) / 16u, 1024u, 0u);
+  hipLaunchKernelGGL(rx_final_compact_kernel, dim3((n_streams + 15u) / 16u), dim3(1024), 0, s, rows,
                      n_streams, row_words, states, cap, off, cnt, counter);
   return (int)hipGetLastError();
 }
@@ -2862,7 +2875,7 @@ int rx_start_capacity(uint32_t size, size_t lds_per_cu) {
 }
 
 int rx_launch_starts(const RxParams& launched, const RxStartArgs& a, int cu_count, size_t lds_per_cu, void* hip_stream,
-                     bool count_on_device) {
+                     bool count_on_device, bool verbose) {
   if (a.n_events == 0) return 0;
   RxParams p = launched;  // the launch's batch (bytes, slots, start rows, k_base); the carve is the start kernel's own
   const uint32_t nw32 = (p.size + 31u) / 32u;
@@ -2881,6 +2894,7 @@ int rx_launch_starts(const RxParams& launched, const RxStartArgs& a, int cu_coun
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return (int)e;
     }
+    if (verbose) log_launch(reinterpret_cast<const void*>(kern), s, grid, wpb * 64u, lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(wpb * 64u), lds, s, p, a);
     return (int)hipGetLastError();
   };
@@ -2889,25 +2903,30 @@ int rx_launch_starts(const RxParams& launched, const RxStartArgs& a, int cu_coun
 }
 
 // ---- device-side download -------------------------------------------------------------------------
-int rx_launch_slots_by_id(const RxSlot* slots, uint32_t n, RxSlot* by_id, void* hip_stream) {
+int rx_launch_slots_by_id(const RxSlot* slots, uint32_t n, RxSlot* by_id, void* hip_stream, bool verbose) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(rx_slots_by_id_kernel, dim3((n + 255u) / 256u), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), slots,
-                     n, by_id);
+  hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+  if (verbose) log_launch(reinterpret_cast<const void*>(rx_slots_by_id_kernel), s, (n + 255u) / 256u, 256u, 0u);
+  hipLaunchKernelGGL(rx_slots_by_id_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, slots, n, by_id);
   return (int)hipGetLastError();
 }
 
-int rx_launch_device_results(const RxSortArgs& a, bool sort, void* hip_stream) {
+int rx_launch_device_results(const RxSortArgs& a, bool sort, void* hip_stream, bool verbose) {
   hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
   hipError_t e;
   for (uint32_t pass = 0; sort && pass < a.n_passes; pass++) {
+    if (verbose) log_launch(reinterpret_cast<const void*>(rx_sort_hist_kernel), s, a.grid, 256u, 0u);
     hipLaunchKernelGGL(rx_sort_hist_kernel, dim3(a.grid), dim3(256), 0, s, a, pass);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if (verbose) log_launch(reinterpret_cast<const void*>(rx_sort_scan_kernel), s, 1u, 256u, 0u);
     hipLaunchKernelGGL(rx_sort_scan_kernel, dim3(1), dim3(256), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if (verbose) log_launch(reinterpret_cast<const void*>(rx_sort_scatter_kernel), s, a.grid, 256u, 0u);
     hipLaunchKernelGGL(rx_sort_scatter_kernel, dim3(a.grid), dim3(256), 0, s, a, pass);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   }
   const uint32_t blocks = a.out_off ? a.n_streams / 256u + 1u : 1u;  // n_streams + 1 offsets
+  if (verbose) log_launch(reinterpret_cast<const void*>(rx_sort_finish_kernel), s, blocks, 256u, 0u);
   hipLaunchKernelGGL(rx_sort_finish_kernel, dim3(blocks), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
@@ -2968,7 +2987,8 @@ static int launch_one(K kern, const RxParams& p, uint32_t grid, uint32_t block, 
   if (g_verbose) {
     int nb = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, (int)block, lds);
-    fprintf(stderr, "[rxmatch] grid %u x %u threads, %u B LDS/block -> %d blocks/CU resident\n", grid, block, lds, nb);
+    fprintf(stderr, "[rxmatch] launch %s grid %u x %u threads, %u B LDS/block -> %d blocks/CU resident\n",
+            kernel_name(reinterpret_cast<const void*>(kern), s), grid, block, lds, nb);
   }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, p);
   return (int)hipGetLastError();

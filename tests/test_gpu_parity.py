@@ -17,7 +17,8 @@ N = 200000
 
 @pytest.fixture(scope="module")
 def kernels(rx):
-    """Every kernel variant the C-ABI can launch, as rx_opts keyword sets."""
+    """One or more builds of every kernel, as rx_opts keyword sets (not every build: test_gpu_kernel_census.py runs each
+    kernel of the code object and checks which one ran)."""
     return [dict(kernel=rx.KERNEL_CSR_WAVE), dict(kernel=rx.KERNEL_SYM_WAVE),
             dict(kernel=rx.KERNEL_SYM_GROUP, group_lanes=1), dict(kernel=rx.KERNEL_SYM_GROUP, group_lanes=2),
             dict(kernel=rx.KERNEL_SYM_GROUP, group_lanes=4), dict(kernel=rx.KERNEL_SYM_GROUP, group_lanes=8),
@@ -136,6 +137,8 @@ def test_synthetic_batches(rx, orx, automata, traces, gpu_nfas, kernels, workloa
         check_equal(rx, orx, got, ref, (workload, kern))
         got = rx.match(gpu_nfas["snort_16"], rows, **kern, want_match_count=True)  # the build without statistics
         check_equal(rx, orx, got, ref, (workload, kern, "plain"), stats=False)
+        if kern.get("flags", 0) & rx.host.OPT_FORCE_FOLD:  # (snort_16 has a foldable state: the FOLD build ran)
+            assert "+fold" in got["stats"]["variant"], (workload, kern, got["stats"]["variant"])
 
 
 def test_ragged_and_edge_shapes(rx, orx, automata, traces, gpu_nfas, kernels):

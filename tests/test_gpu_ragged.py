@@ -1,8 +1,10 @@
 """Ragged batches on the GPU (rx_match_ragged, rx_plan_upload_ragged, rx_plan_set_device_input_ragged): every output of
-stream s equals what the oracle returns for that stream alone, on every kernel that takes ragged batches."""
+stream s equals what the oracle returns for that stream alone, on every kernel that takes ragged batches.  The kernel lists
+below are a sample of the builds; test_gpu_kernel_census.py runs every ragged build and checks which one ran."""
 import numpy as np
 import pytest
 
+from kernel_census import handed_off
 from nfa_util import blowup_nfa, kat_ab, late_blowup_nfa
 from ragged_util import check_equal, ragged_offsets, ragged_ref
 
@@ -95,15 +97,6 @@ def test_equal_lengths_match_uniform(rx, orx, automata, traces, kernels):
                 assert a["stats"][k] == b["stats"][k], (mode, kern, k)
 
 
-def handed_off(capfd):
-    """Streams the first launch handed to the wave kernel, from RX_OPT_VERBOSE's line on stderr."""
-    err = capfd.readouterr().err
-    for line in err.splitlines():
-        if "were handed to the wave kernel" in line:
-            return int(line.split("] ")[1].split()[0])
-    return 0
-
-
 @pytest.mark.parametrize("n_streams", [40, 5000])
 def test_handoffs(rx, orx, kernels, n_streams, capfd):
     """Streams that outgrow the pack / register kernels' lists before, at and after other streams' ends, including in their
@@ -134,7 +127,7 @@ def test_handoffs(rx, orx, kernels, n_streams, capfd):
     capfd.readouterr()
     got = rx.match_ragged(nfa, data, off, kernel=rx.KERNEL_SYM_PACK, group_lanes=13, flags=rx.host.OPT_VERBOSE)
     check_equal(rx, orx, got, ragged_ref(orx, W, size, data, off, rx.MODE_FULL), ("handoff count", n_streams), stats=False)
-    n = handed_off(capfd)
+    n = handed_off(capfd.readouterr().err)
     assert n >= (26 if n_streams == 40 else 4097), n
     W, size = blowup_nfa(300)
     nfa = rx.Nfa.from_words(W)
