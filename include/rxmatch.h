@@ -96,6 +96,14 @@ int rx_compile_patterns(const char* const* patterns, size_t n, uint32_t flags, r
                         size_t errbuf_len);
 /* Pattern index an accept state reports (-1: not an accept state / table was not compiled here). */
 int rx_nfa_accept_pattern(const rx_nfa* nfa, uint32_t state, int32_t* pattern_index);
+/* Patterns of the automaton's pattern map (the map above): max over the states of their pattern index, plus one; 0 for an
+ * automaton without a map (loaded from a .coe or from words). */
+int rx_nfa_pattern_count(const rx_nfa* nfa, uint32_t* n_patterns);
+/* A new, independent handle: src's table plus the pattern map pattern_of_state[0 .. n_states) (src may be freed afterwards;
+ * rx_nfa_accept_pattern of the new handle returns the map).  RX_EINVAL when n_states != size, for an entry below -1 or at
+ * least 2^24, and for a state that is not an accept state (it has out-edges) with an entry >= 0.  Several accept states may
+ * name one pattern. */
+int rx_nfa_with_accept_patterns(const rx_nfa* src, const int32_t* pattern_of_state, size_t n_states, rx_nfa** out);
 /* Writes the table as a Xilinx .coe in the layout of Block_Mem/CSR_BlockMem_snort_16.coe
  * (radix 16, one 128-bit line per row of text) so it can initialise the reference's ROM. */
 int rx_nfa_save_coe(const rx_nfa* nfa, const char* path);
@@ -181,7 +189,9 @@ enum {
   RX_OPT_NO_PROBE = 256u,   /* RX_KERNEL_AUTO never probes inside rx_plan_launch / rx_plan_run: no sample launches, no
                                timed candidates, no stream synchronisation.  The decision is the one rx_plan_tune made
                                for the shape, or a default (SYM_PACK, 16 streams per wavefront; SYM_REG up to 4 streams) */
-  RX_OPT_RAGGED_NO_SORT = 512u /* ragged batches: streams go to wavefront slots in the caller's order, not longest first (A/B) */
+  RX_OPT_RAGGED_NO_SORT = 512u, /* ragged batches: streams go to wavefront slots in the caller's order, not longest first (A/B) */
+  RX_OPT_PATTERNS = 1024u    /* rx_plan_create: record per-pattern hits on every launch (rx_plan_download_patterns); the
+                               automaton must have a pattern map (RX_EINVAL, before any device work, otherwise) */
 };
 
 /* One accept pulse: `state` was active and accepting in pass `k` of stream `stream`.
@@ -381,6 +391,38 @@ typedef struct rx_device_result {
   uint64_t* final_active;
 } rx_device_result;
 int rx_plan_download_device(rx_plan* plan, rx_device_result* res);
+/* Per-pattern results of the last launch of a plan created with RX_OPT_PATTERNS.  map[a] = rx_nfa_accept_pattern(a),
+ * n_patterns = rx_nfa_pattern_count, pw = ceil(n_patterns / 64).  Bit p of stream s's row hits[s * pw + p / 64] (bit p % 64)
+ * is set iff an accept pulse of a state a with map[a] == p happened in stream s during the launch's passes: the pulses
+ * rx_stats.n_events counts (the mode's passes of this batch only; all of them, those beyond events_cap included).  Bits at or
+ * beyond n_patterns are 0.  count_total[p] = the pulses of pattern p over all streams (= the sum of match_count_total over
+ * the states of p).  The same hits as compact lists, like the compact final sets: the patterns of stream s are
+ * ids[off[s] .. off[s] + cnt[s]), ascending; cnt is exact, off names only the part that was written.  Rows are indexed by
+ * the caller's stream index, also for ragged batches.  Every array is optional; ids/off/cnt come all three or none. */
+typedef struct rx_pattern_result {
+  uint32_t struct_size;      /* = sizeof(rx_pattern_result) */
+  uint32_t n_patterns;       /* out */
+  uint64_t* hits;            /* [n_streams][pw] or NULL */
+  uint64_t* count_total;     /* [n_patterns] or NULL */
+  uint32_t* ids;             /* [ids_cap] */
+  uint32_t* off;             /* [n_streams] */
+  uint32_t* cnt;             /* [n_streams] */
+  size_t ids_cap;            /* < 2^32 */
+  size_t n_ids;              /* out (host variant): ids written, min(total, ids_cap) */
+  uint32_t ids_overflow;     /* out (host variant): 1 if the total exceeded ids_cap */
+  uint32_t reserved0;
+  uint64_t* ids_total;       /* [1] or NULL, device variant with the lists: the number of ids in all
+                                (overflow: *ids_total > ids_cap) */
+} rx_pattern_result;
+/* Into the caller's host arrays (waits for the launch).  RX_ESTATE without a launch, after rx_plan_run and for a plan
+ * created without RX_OPT_PATTERNS; RX_EINVAL for a partial list triple or a struct_size below sizeof(rx_pattern_result). */
+int rx_plan_download_patterns(rx_plan* plan, rx_pattern_result* res);
+/* The same into the caller's DEVICE memory, enqueued on the plan's stream behind the launch without any host wait (as
+ * rx_plan_download_device): the arrays equal the host variant's byte for byte (ids: the first min(*ids_total, ids_cap); the
+ * rest of the array is unspecified).  n_patterns is written; n_ids and ids_overflow are left 0 (the device knows them:
+ * ids_total).  The lists of a launch are made once per ids_cap, so both variants return them in the same order.  Checks as
+ * the host variant, and RX_EINVAL for a pointer that is not device memory of the plan's device. */
+int rx_plan_download_patterns_device(rx_plan* plan, rx_pattern_result* res);
 /* Host buffers in, host results out, in ONE call — the same results as rx_plan_upload + rx_plan_launch +
  * rx_plan_download, but pipelined: the batch is cut into up to 8 blocks of >= 32 768 streams that share three HIP
  * streams (uploads, kernels, downloads), so that the upload of block i+1, the kernel of block i and the download of

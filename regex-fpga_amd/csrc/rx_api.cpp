@@ -219,6 +219,38 @@ extern "C" int rx_nfa_accept_pattern(const rx_nfa* nfa, uint32_t state, int32_t*
   RX_CATCH
 }
 
+static uint32_t pattern_count(const rx_nfa* nfa) {
+  int32_t top = -1;
+  for (int32_t q : nfa->accept_pattern) top = std::max(top, q);
+  return (uint32_t)(top + 1);
+}
+
+extern "C" int rx_nfa_pattern_count(const rx_nfa* nfa, uint32_t* n_patterns) {
+  RX_TRY
+  if (!nfa || !n_patterns) return RX_EINVAL;
+  *n_patterns = pattern_count(nfa);
+  return RX_OK;
+  RX_CATCH
+}
+
+extern "C" int rx_nfa_with_accept_patterns(const rx_nfa* src, const int32_t* pattern_of_state, size_t n_states, rx_nfa** out) {
+  RX_TRY
+  if (!src || !pattern_of_state || !out || n_states != src->h.size) return RX_EINVAL;
+  const RxHostNfa& h = src->h;
+  for (size_t a = 0; a < n_states; a++) {
+    const int32_t q = pattern_of_state[a];
+    const bool accept = (h.accept_bits[a >> 5] >> (a & 31)) & 1u;
+    if (q < -1 || q >= (1 << 24) || (q >= 0 && !accept)) return RX_EINVAL;
+  }
+  // the same table and host index, copied (the device copies are made on first use, as for any handle)
+  std::unique_ptr<rx_nfa> n(new rx_nfa());
+  n->h = h;
+  n->accept_pattern.assign(pattern_of_state, pattern_of_state + n_states);
+  *out = n.release();
+  return RX_OK;
+  RX_CATCH
+}
+
 extern "C" int rx_nfa_save_coe(const rx_nfa* nfa, const char* path) {
   RX_TRY
   if (!nfa || !path) return RX_EINVAL;
@@ -463,6 +495,16 @@ struct rx_plan {
   HipBuf<unsigned long long> d_sort_key;
   HipBuf<uint32_t> d_sort_val, d_sort_hist, d_dev_starts;
   HipBuf<RxSlot> d_dev_by_id;
+  // per-pattern hits (RX_OPT_PATTERNS): the map on the device, one row of pat_words per stream (cleared by every launch), the
+  // totals in the counter sets behind match_count_total; the lists of the last launch (ids, off, cnt, count), compacted once
+  // per launch and capacity into this scratch (grown on demand), from which both downloads copy
+  bool want_pat = false;
+  uint32_t n_pat = 0, pat_words = 0;
+  bool pat_lists_valid = false;
+  size_t pat_lists_cap = 0;
+  HipBuf<int32_t> d_pat_of;
+  HipBuf<unsigned long long> d_pat_rows, d_pat_ctr;
+  HipBuf<uint32_t> d_pat_ids, d_pat_off, d_pat_cnt;
   size_t am_stride = 0;
   // current batch
   size_t n_streams = 0, stream_len = 0, stride = 0;
@@ -543,6 +585,9 @@ static uint64_t passes_for(size_t n, uint32_t mode) {
   return (uint64_t)n + 1;
 }
 
+// words of one counter set: counters[16], match_count_total[size], and with RX_OPT_PATTERNS the pattern totals[n_patterns]
+static size_t counter_set_words(const rx_plan* p) { return 16 + (size_t)p->nfa->h.size + p->n_pat; }
+
 static int bind_device(int device, int* resolved) {
   if (device < 0) {
     HIPCHK(hipGetDevice(resolved));
@@ -562,6 +607,9 @@ extern "C" int rx_plan_create(const rx_nfa* nfa, const rx_opts* opts, size_t max
     return RX_ECAPACITY;
   const rx_opts o = read_opts(opts);
   if (o.mode > RX_MODE_TB_COMPAT) return RX_EINVAL;
+  const bool want_pat = (o.flags & RX_OPT_PATTERNS) != 0;
+  const uint32_t n_pat = pattern_count(nfa);
+  if (want_pat && n_pat == 0) return RX_EINVAL;  // (no pattern map: .coe / words without rx_nfa_with_accept_patterns)
   // rx_event.k and the kernels' pass counters are 32 bits wide: a chained stream may not run past 2^32 passes
   if (o.k_base + passes_for(max_stream_len, RX_MODE_FULL) > (1ull << 32)) return RX_EINVAL;
   int ndev = 0;
@@ -581,12 +629,15 @@ extern "C" int rx_plan_create(const rx_nfa* nfa, const rx_opts* opts, size_t max
   p->want_mc = want_match_count != 0;
   p->want_am = want_anymatch != 0;
   p->want_final = want_final != 0;
+  p->want_pat = want_pat;
+  p->n_pat = want_pat ? n_pat : 0;
+  p->pat_words = (p->n_pat + 63u) / 64u;
   int rc = bind_device(o.device, &p->device);
   if (rc) return rc;
   rc = get_dev_tables(nfa, p->device, &p->tab);
   if (rc) return rc;
   const uint32_t size = nfa->h.size;
-  const size_t nw64x2 = 2 * (((size_t)size + 63) / 64), set_words = 16 + (size_t)size;
+  const size_t nw64x2 = 2 * (((size_t)size + 63) / 64), set_words = counter_set_words(p.get());
   for (auto& set : p->d_cset) {
     if ((rc = set.grow(set_words))) return rc;
     HIPCHK(hipMemset(set.p, 0, set_words * sizeof(unsigned long long)));
@@ -601,6 +652,10 @@ extern "C" int rx_plan_create(const rx_nfa* nfa, const rx_opts* opts, size_t max
   p->am_stride = ((size_t)((passes_for(max_stream_len, RX_MODE_FULL) + 31) / 32) + 7) & ~(size_t)7;
   if (p->want_am && (rc = p->d_am.grow(max_streams * p->am_stride))) return rc;
   if (p->want_final && (rc = p->d_final.grow(max_streams * nw64x2))) return rc;
+  if (want_pat) {
+    if ((rc = p->d_pat_of.grow(size)) || (rc = p->d_pat_rows.grow(max_streams * p->pat_words))) return rc;
+    HIPCHK(hipMemcpy(p->d_pat_of.p, nfa->accept_pattern.data(), (size_t)size * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
   *out = p.release();
   return RX_OK;
   RX_CATCH
@@ -1136,6 +1191,11 @@ static int batch_params(rx_plan* p) {
   a.anymatch = p->want_am ? p->d_am.p : nullptr;
   a.anymatch_stride = (uint32_t)p->am_stride;
   a.final_active = p->want_final ? p->d_final.p : nullptr;
+  if (p->want_pat) {
+    a.pat_of = p->d_pat_of.p;
+    a.pat_rows = p->d_pat_rows.p;
+    a.pat_words = p->pat_words;
+  }
   a.slots = p->ragged ? p->d_slots.p : nullptr;
   // the testbench's clock count needs both streams of a pair in one wavefront: pack kernel only
   const bool pair = p->opts.collect_stats == 2;
@@ -1306,7 +1366,7 @@ extern "C" int rx_plan_launch(rx_plan* p) {
 
   // counters + match_count_total: the other set, which the previous launch's kernel has zeroed (or, after a probe or
   // the plan's creation, a reset enqueued here); this launch's kernel zeroes the one after
-  const size_t set_words = 16 + (size_t)h.size;
+  const size_t set_words = counter_set_words(p);
   if (!p->sets_clean) {
     for (auto& set : p->d_cset) HIPCHK(hipMemsetAsync(set.p, 0, set_words * sizeof(unsigned long long), p->stream));
     p->sets_clean = true;
@@ -1317,10 +1377,13 @@ extern "C" int rx_plan_launch(rx_plan* p) {
   a.counters = p->d_counters;
   a.ev_count = p->d_counters;
   a.match_count_total = p->d_mct;
+  if (a.pat_rows) a.pat_total = p->d_mct + h.size;
   if (a.spill_count) a.spill_count = p->d_counters + 3;
   a.zero_next = p->d_cset[p->cur_set ^ 1].p;
   a.zero_words = (uint32_t)set_words;
   if (p->want_mc) HIPCHK(hipMemsetAsync(p->d_mc.p, 0, p->n_streams * h.size * sizeof(uint32_t), p->stream));
+  if (p->want_pat) HIPCHK(hipMemsetAsync(p->d_pat_rows.p, 0, p->n_streams * p->pat_words * sizeof(unsigned long long), p->stream));
+  p->pat_lists_valid = false;
   // ragged batch: the kernels write a stream's any-match words up to its own last pass; the rest of the row reads 0
   if (p->ragged && p->want_am) HIPCHK(hipMemsetAsync(p->d_am.p, 0, p->n_streams * p->am_stride * sizeof(uint32_t), p->stream));
   if (p->n_timed >= 4096) p->n_timed = 0;  // nobody is reading the times: recycle the pool
@@ -1780,6 +1843,98 @@ extern "C" int rx_plan_download_device(rx_plan* p, rx_device_result* res) {
   RX_CATCH
 }
 
+// ---- per-pattern results (RX_OPT_PATTERNS) -----------------------------------------------------------
+// The checks both variants make before anything is enqueued
+static int patterns_check(const rx_plan* p, const rx_pattern_result* res) {
+  if (!p || !res || res->struct_size < sizeof(rx_pattern_result)) return RX_EINVAL;
+  const int lists = (res->ids != nullptr) + (res->off != nullptr) + (res->cnt != nullptr);
+  if ((lists != 0 && lists != 3) || res->ids_cap > 0xFFFFFFFFull) return RX_EINVAL;
+  if (!p->launched || !p->want_pat) return RX_ESTATE;
+  return RX_OK;
+}
+
+// The hits as lists: the compaction kernel of the final sets over the rows viewed as 2 * pat_words u32 words (bit q of u64
+// word w is bit q % 32 of u32 word 2w + q / 32: entry 64w + q, the pattern id), into the plan's scratch, capacity
+// min(ids_cap, all hits possible); d_pat_ctr ends as the total.  The order in which the kernel's blocks take their place in
+// `ids` is that of their atomics, so the lists are made ONCE per launch and capacity and both downloads copy from them: the
+// device variant returns the host variant's bytes.
+static int pattern_lists(rx_plan* p, size_t ids_cap) {
+  const size_t cap = std::min<size_t>(ids_cap, p->n_streams * (size_t)p->n_pat);
+  if (p->pat_lists_valid && p->pat_lists_cap == cap) return RX_OK;
+  int rc;
+  if ((rc = p->d_pat_ctr.grow(1)) || (rc = p->d_pat_ids.grow(std::max<size_t>(cap, 1))) || (rc = p->d_pat_off.grow(p->max_streams)) ||
+      (rc = p->d_pat_cnt.grow(p->max_streams)))
+    return rc;
+  HIPCHK(hipMemsetAsync(p->d_pat_ctr.p, 0, sizeof(unsigned long long), p->stream));
+  const hipError_t e = (hipError_t)rx_launch_final_compact(reinterpret_cast<const uint32_t*>(p->d_pat_rows.p), (uint32_t)p->n_streams,
+                                                           2u * p->pat_words, p->d_pat_ids.p, (uint32_t)cap, p->d_pat_off.p,
+                                                           p->d_pat_cnt.p, p->d_pat_ctr.p, p->stream, (p->opts.flags & RX_OPT_VERBOSE) != 0);
+  if (e != hipSuccess) return hip_fail(e, "pattern list compaction launch");
+  p->pat_lists_valid = true;
+  p->pat_lists_cap = cap;
+  return RX_OK;
+}
+
+extern "C" int rx_plan_download_patterns(rx_plan* p, rx_pattern_result* res) {
+  RX_TRY
+  int rc = patterns_check(p, res);
+  if (rc) return rc;
+  int dev;
+  if ((rc = bind_device(p->device, &dev))) return rc;
+  const size_t n = p->n_streams;
+  res->n_patterns = p->n_pat;
+  res->n_ids = 0;
+  res->ids_overflow = 0;
+  if (res->ids && (rc = pattern_lists(p, res->ids_cap))) return rc;
+  HIPCHK(hipStreamSynchronize(p->stream));
+  if (res->hits) HIPCHK(hipMemcpy(res->hits, p->d_pat_rows.p, n * p->pat_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (res->count_total)
+    HIPCHK(hipMemcpy(res->count_total, p->d_mct + p->nfa->h.size, (size_t)p->n_pat * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (res->ids) {
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpy(&total, p->d_pat_ctr.p, sizeof(total), hipMemcpyDeviceToHost));
+    res->n_ids = (size_t)std::min<unsigned long long>(total, res->ids_cap);
+    res->ids_overflow = total > res->ids_cap ? 1u : 0u;
+    if (res->n_ids) HIPCHK(hipMemcpy(res->ids, p->d_pat_ids.p, res->n_ids * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(res->off, p->d_pat_off.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(res->cnt, p->d_pat_cnt.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  return RX_OK;
+  RX_CATCH
+}
+
+extern "C" int rx_plan_download_patterns_device(rx_plan* p, rx_pattern_result* res) {
+  RX_TRY
+  int rc = patterns_check(p, res);
+  if (rc) return rc;
+  int dev;
+  if ((rc = bind_device(p->device, &dev))) return rc;
+  for (const void* q : {(const void*)res->hits, (const void*)res->count_total, (const void*)res->ids, (const void*)res->off,
+                        (const void*)res->cnt, (const void*)res->ids_total})
+    if (!on_plan_device(p, q)) return RX_EINVAL;
+  const size_t n = p->n_streams;
+  res->n_patterns = p->n_pat;
+  res->n_ids = 0;
+  res->ids_overflow = 0;
+  if (res->ids) {
+    if ((rc = pattern_lists(p, res->ids_cap))) return rc;
+    // (the whole capacity: how many of them are ids only the device knows)
+    const size_t cap = p->pat_lists_cap;
+    if (cap) HIPCHK(hipMemcpyAsync(res->ids, p->d_pat_ids.p, cap * sizeof(uint32_t), hipMemcpyDeviceToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(res->off, p->d_pat_off.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(res->cnt, p->d_pat_cnt.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, p->stream));
+    if (res->ids_total)
+      HIPCHK(hipMemcpyAsync(res->ids_total, p->d_pat_ctr.p, sizeof(uint64_t), hipMemcpyDeviceToDevice, p->stream));
+  }
+  if (res->hits)
+    HIPCHK(hipMemcpyAsync(res->hits, p->d_pat_rows.p, n * p->pat_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, p->stream));
+  if (res->count_total)
+    HIPCHK(hipMemcpyAsync(res->count_total, p->d_mct + p->nfa->h.size, (size_t)p->n_pat * sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                          p->stream));
+  return RX_OK;
+  RX_CATCH
+}
+
 // ---- pipelined host-to-host run ---------------------------------------------------------------------
 extern "C" int rx_host_register(void* ptr, size_t bytes) {
   if (!ptr || !bytes) return RX_EINVAL;
@@ -1922,6 +2077,8 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
     a.match_count_total = q.d_set.p + 16;
     a.zero_next = nullptr;
     a.zero_words = 0;
+    a.pat_rows = nullptr;  // (per-pattern hits: rx_plan_launch only)
+    a.pat_total = nullptr;
     if (a.match_count) a.match_count += s0 * size;
     if (a.anymatch) a.anymatch += s0 * p->am_stride;
     if (a.final_active) a.final_active += s0 * (size_t)a.nw64x2;
@@ -2077,6 +2234,14 @@ static int plan_run_body(rx_plan* p, const uint8_t* bytes, size_t n_streams, siz
 }
 
 // ---- one-shot -------------------------------------------------------------------------------------
+// The one-shot calls have no per-pattern results: their plans are made without RX_OPT_PATTERNS
+static rx_opts one_shot_opts(const rx_opts* opts) {
+  rx_opts o = read_opts(opts);
+  o.struct_size = sizeof(rx_opts);
+  o.flags &= ~(uint32_t)RX_OPT_PATTERNS;
+  return o;
+}
+
 extern "C" int rx_match(const rx_nfa* nfa, const uint8_t* bytes, size_t n_streams, size_t stream_len, size_t stride,
                         const uint64_t* init_active, const rx_opts* opts, rx_result* res) {
   RX_TRY
@@ -2089,7 +2254,8 @@ extern "C" int rx_match(const rx_nfa* nfa, const uint8_t* bytes, size_t n_stream
   const bool has_compact = result_bytes(res) >= offsetof(rx_result, final_states_overflow) + sizeof(uint32_t);
   const bool starts = starts_of(res) != nullptr;
   if (has_compact && res->final_states && (init_active || starts)) return RX_EINVAL;
-  int rc = rx_plan_create(nfa, opts, n_streams, stream_len, res->events ? res->events_cap : 0,
+  const rx_opts o = one_shot_opts(opts);
+  int rc = rx_plan_create(nfa, &o, n_streams, stream_len, res->events ? res->events_cap : 0,
                           res->match_count != nullptr, res->anymatch != nullptr,
                           res->final_active != nullptr || (has_compact && res->final_states != nullptr), &p);
   if (rc) return rc;
@@ -2146,7 +2312,8 @@ extern "C" int rx_match_ragged(const rx_nfa* nfa, const uint8_t* bytes, const ui
   if (res->anymatch && res->anymatch_stride < (size_t)((passes_for(longest, o.mode) + 31) / 32)) return RX_EINVAL;
   if (!starts_ok(res)) return RX_EINVAL;
   rx_plan* p = nullptr;
-  int rc = rx_plan_create(nfa, opts, n_streams, longest, res->events ? res->events_cap : 0,
+  const rx_opts po = one_shot_opts(opts);
+  int rc = rx_plan_create(nfa, &po, n_streams, longest, res->events ? res->events_cap : 0,
                           res->match_count != nullptr, res->anymatch != nullptr, res->final_active != nullptr, &p);
   if (rc) return rc;
   auto done = [&](int code) {

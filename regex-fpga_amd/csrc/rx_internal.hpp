@@ -119,6 +119,12 @@ struct RxParams {
   uint32_t* anymatch;           // [n_streams][anymatch_stride] or null
   uint32_t anymatch_stride;
   uint32_t* final_active;       // [n_streams][nw64x2] or null
+  // Per-pattern hits (RX_OPT_PATTERNS): every accept pulse of state a with pat_of[a] = q >= 0 sets bit q of the stream's row
+  // pat_rows[stream * pat_words ..] and counts in pat_total[q].  Null for plans without the flag, AUTO's probes, rx_plan_run.
+  const int32_t* pat_of;        // [size]
+  unsigned long long* pat_rows; // [n_streams][pat_words]
+  unsigned long long* pat_total;// [n_patterns], in the launch's counter set behind match_count_total
+  uint32_t pat_words;           // ceil(n_patterns / 64)
   // The final sets as compact lists, written by the match kernel itself (pack kernel and the wave kernel that finishes its
   // hand-offs; rx_plan_run on request): states of stream s ascending at fin_states[fin_off[s] .. + fin_cnt[s]), space taken
   // from *fin_count (one atomic per wavefront), entries at or beyond fin_cap not written.  When set, no rows are written.

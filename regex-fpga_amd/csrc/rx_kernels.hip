@@ -214,6 +214,20 @@ __device__ __forceinline__ void emit_events(const RxParams& p, bool acc, uint32_
     }
     if (p.match_count) atomicAdd(&p.match_count[(size_t)stream * p.size + state], 1u);
     if (p.match_count_total) atomicAdd(&p.match_count_total[state], 1ull);
+    // per-pattern hits (RX_OPT_PATTERNS): the stream's bit of the state's pattern, and its pulse count.  The fields are read
+    // here, from the kernel-argument segment (cold_params): held in SGPRs across the pass loops they cost the hot kernels
+    // occupancy.
+    // The row is set as u32 words (bit q of a little-endian u64 row is bit q % 32 of its u32 word q / 32): a 32-bit
+    // operand where a 64-bit one would cost the pack kernels a VGPR pair and a wave of occupancy.
+    const RxColdParams c = cold_params();
+    if (c->pat_rows) {
+      const int32_t q = c->pat_of[state];
+      if (q >= 0) {
+        atomicAdd(&c->pat_total[q], 1ull);
+        uint32_t* const row = reinterpret_cast<uint32_t*>(c->pat_rows + (size_t)stream * c->pat_words);
+        atomicOr(&row[(uint32_t)q >> 5], 1u << ((uint32_t)q & 31u));
+      }
+    }
   }
   am_word |= 1u << (k & 31u);
 }

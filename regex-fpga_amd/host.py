@@ -18,7 +18,7 @@ KERNEL_NAMES = {0: "auto", 1: "csr_wave", 2: "sym_wave", 3: "sym_group", 4: "sym
 
 # rx_opts.flags (A/B and diagnostic switches; read at plan creation, never from the environment)
 OPT_NO_PRUNE, OPT_FORCE_PRUNE, OPT_VERBOSE, OPT_PROFILE_PACK, OPT_NO_FOLD, OPT_FORCE_FOLD, OPT_REG_NO_SKIP = 1, 2, 4, 8, 16, 32, 64
-OPT_INJECT_RUN_FAULT, OPT_NO_PROBE, OPT_RAGGED_NO_SORT = 128, 256, 512
+OPT_INJECT_RUN_FAULT, OPT_NO_PROBE, OPT_RAGGED_NO_SORT, OPT_PATTERNS = 128, 256, 512, 1024
 
 EVENT_DT = np.dtype([("stream", "<u4"), ("k", "<u4"), ("state", "<u4")])
 
@@ -62,6 +62,12 @@ class _DeviceResult(C.Structure):
                 ("final_active", C.c_void_p)]
 
 
+class _PatternResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_patterns", C.c_uint32), ("hits", C.c_void_p), ("count_total", C.c_void_p),
+                ("ids", C.c_void_p), ("off", C.c_void_p), ("cnt", C.c_void_p), ("ids_cap", C.c_size_t), ("n_ids", C.c_size_t),
+                ("ids_overflow", C.c_uint32), ("reserved0", C.c_uint32), ("ids_total", C.c_void_p)]
+
+
 # rx_result.event_start: the match began before the batch (a chained stream's earlier part); see include/rxmatch.h
 START_BEFORE = 0xFFFFFFFF
 
@@ -80,7 +86,8 @@ ABI_SYMBOLS = ["rx_nfa_dfa_info", "rx_nfa_dfa_reset", "rx_compile_patterns", "rx
                "rx_plan_set_init_active", "rx_plan_launch", "rx_plan_sync", "rx_plan_kernel_times", "rx_plan_download", "rx_plan_free",
                "rx_device_count", "rx_device_name", "rx_plan_run", "rx_host_register", "rx_host_unregister", "rx_plan_tune",
                "rx_plan_busy", "rx_match_ragged", "rx_plan_upload_ragged", "rx_plan_set_device_input_ragged",
-               "rx_plan_download_device"]
+               "rx_plan_download_device", "rx_nfa_pattern_count", "rx_nfa_with_accept_patterns", "rx_plan_download_patterns",
+               "rx_plan_download_patterns_device"]
 
 _lib = None
 
@@ -162,6 +169,11 @@ def lib():
     L.rx_plan_run.argtypes = [vp, vp, sz, sz, sz, C.POINTER(_Result)]
     if hasattr(L, "rx_plan_download_device"):  # (likewise)
         L.rx_plan_download_device.argtypes = [vp, C.POINTER(_DeviceResult)]
+    if hasattr(L, "rx_plan_download_patterns"):  # (likewise)
+        L.rx_nfa_pattern_count.argtypes = [vp, C.POINTER(u32)]
+        L.rx_nfa_with_accept_patterns.argtypes = [vp, vp, sz, C.POINTER(vp)]
+        L.rx_plan_download_patterns.argtypes = [vp, C.POINTER(_PatternResult)]
+        L.rx_plan_download_patterns_device.argtypes = [vp, C.POINTER(_PatternResult)]
     L.rx_host_register.argtypes = [vp, sz]
     L.rx_host_unregister.argtypes = [vp]
     L.rx_plan_free.argtypes = [vp]
@@ -238,6 +250,22 @@ class Nfa:
         out = C.c_int32(-1)
         _chk(lib().rx_nfa_accept_pattern(self._h, int(state), C.byref(out)), "rx_nfa_accept_pattern")
         return out.value
+
+    @property
+    def pattern_count(self):
+        """rx_nfa_pattern_count(): patterns of the pattern map (0: the automaton has none)."""
+        n = C.c_uint32()
+        _chk(lib().rx_nfa_pattern_count(self._h, C.byref(n)), "rx_nfa_pattern_count")
+        return n.value
+
+    def with_accept_patterns(self, pattern_of_state):
+        """rx_nfa_with_accept_patterns(): a new automaton, this table plus the map (int32 [size]: the pattern of every
+        accept state, -1 elsewhere)."""
+        m = np.ascontiguousarray(pattern_of_state, dtype=np.int32)
+        h = C.c_void_p()
+        _chk(lib().rx_nfa_with_accept_patterns(self._h, m.ctypes.data_as(C.c_void_p), m.size, C.byref(h)),
+             "rx_nfa_with_accept_patterns")
+        return Nfa(h)
 
     def dfa_info(self, device=0):
         """(states, transitions) of the lazy-DFA cache built so far on `device`."""
@@ -518,13 +546,38 @@ def device_result_arrays(out, dev, n_streams, size, nw64, nw, cap, starts, want_
                 final_active=take("final_active", i64, n_streams, nw64) if want_final else None), cap
 
 
+def pattern_result_arrays(out, dev, n_streams, n_patterns, ids_cap):
+    """The torch tensors Plan.download_patterns_device writes: new ones (out None), or those of `out` after checking that each
+    one the call writes is there, on `dev`, of its dtype, contiguous and large enough for the batch — ValueError otherwise
+    (the library writes through bare pointers)."""
+    import torch
+    i32, i64 = torch.int32, torch.int64
+    pw = (n_patterns + 63) // 64
+    want = dict(hits=(i64, n_streams * pw, pw), count_total=(i64, n_patterns, None))
+    if ids_cap > 0:
+        want.update(ids=(i32, ids_cap, None), off=(i32, n_streams, None), cnt=(i32, n_streams, None), ids_total=(i64, 1, None))
+    if out is None:
+        return {k: torch.empty((n // row, row) if row else n, dtype=dt, device=dev) for k, (dt, n, row) in want.items()}
+    got = {}
+    for k, (dt, n, row) in want.items():
+        t = out.get(k)
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"download_patterns_device(out=...): out['{k}'] must be a contiguous {dt} tensor on {dev}")
+        if t.numel() < n or (row and (t.dim() != 2 or t.shape[1] != row)):
+            raise ValueError(f"download_patterns_device(out=...): out['{k}'] is too small for the batch ({list(t.shape)})")
+        got[k] = t
+    return got
+
+
 class Plan:
     """rx_plan: inputs stay resident in HBM across launches (serving / benchmarking)."""
 
     def __init__(self, nfa, max_streams, max_stream_len, mode=MODE_FULL, kernel=KERNEL_AUTO, device=-1, stream=None,
                  events_cap=1 << 20, want_match_count=False, want_anymatch=True, want_final=True, collect_stats=False,
-                 k_base=0, group_lanes=0, flags=0):
+                 k_base=0, group_lanes=0, flags=0, patterns=False):
+        """patterns=True: per-pattern hits on every launch (OPT_PATTERNS; download_patterns / download_patterns_device)."""
         self.nfa, self.mode = nfa, mode
+        flags |= OPT_PATTERNS if patterns else 0
         self.events_cap = events_cap
         self.want = (want_match_count, want_anymatch, want_final)
         self._o = _mk_opts(device, mode, kernel, stream, k_base, collect_stats, group_lanes, flags)
@@ -651,6 +704,58 @@ class Plan:
                     match_count_total=cut(a["match_count_total"], slice(0, self.nfa.size)),
                     anymatch=cut(a["anymatch"], slice(0, ns), slice(0, nw)), final_active=cut(a["final_active"], slice(0, ns)),
                     final_states=None, final_off=None, final_cnt=None, final_states_overflow=False, stats=None)
+
+    def download_patterns(self, ids_cap=0):
+        """rx_plan_download_patterns(): `hits` (uint64 [n_streams, ceil(n_patterns / 64)], bit p of a row: pattern p matched
+        in that stream) and `count_total` (uint64 [n_patterns]: pulses per pattern); with ids_cap > 0 also the lists of at
+        most ids_cap ids in all: `ids` (the ids written), `off`, `cnt` (uint32 [n_streams]: stream s's patterns are
+        ids[off[s]:off[s] + cnt[s]]), `n_ids` and `ids_overflow`."""
+        n_pat = self.nfa.pattern_count
+        hits = np.zeros((self.n_streams, (n_pat + 63) // 64), np.uint64)
+        tot = np.zeros(n_pat, np.uint64)
+        r = _PatternResult()
+        r.struct_size = C.sizeof(_PatternResult)
+        r.hits, r.count_total = hits.ctypes.data, tot.ctypes.data
+        lists = None
+        if ids_cap > 0:
+            lists = (np.zeros(ids_cap, np.uint32), np.zeros(self.n_streams, np.uint32), np.zeros(self.n_streams, np.uint32))
+            r.ids, r.off, r.cnt = (a.ctypes.data for a in lists)
+            r.ids_cap = ids_cap
+        _chk(lib().rx_plan_download_patterns(self._h, C.byref(r)), "rx_plan_download_patterns")
+        out = dict(hits=hits, count_total=tot, n_patterns=int(r.n_patterns))
+        if lists is not None:
+            out.update(ids=lists[0][:r.n_ids], off=lists[1], cnt=lists[2], n_ids=int(r.n_ids), ids_overflow=bool(r.ids_overflow))
+        return out
+
+    def download_patterns_device(self, ids_cap=0, out=None):
+        """rx_plan_download_patterns_device(): download_patterns()'s arrays as torch tensors on the plan's device (unsigned
+        values as the signed type of their width), enqueued on the plan's stream without any host wait; with ids_cap > 0 also
+        `ids` (int32 [ids_cap], the first min(ids_total, ids_cap) valid), `off`, `cnt` and `ids_total` (int64 [1]: overflow iff
+        > ids_cap).  `out`: a dict an earlier call returned, refilled in place — each tensor the call writes must be there,
+        on the device, of its dtype and large enough (ValueError otherwise).  The streams hand-shake as in download_device."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        pw = (self.nfa.pattern_count + 63) // 64
+        a = pattern_result_arrays(out, dev, self.n_streams, self.nfa.pattern_count, ids_cap)
+        r = _PatternResult()
+        r.struct_size = C.sizeof(_PatternResult)
+        r.hits, r.count_total = a["hits"].data_ptr(), a["count_total"].data_ptr()
+        if ids_cap > 0:
+            r.ids, r.off, r.cnt, r.ids_total = (a[k].data_ptr() for k in ("ids", "off", "cnt", "ids_total"))
+            r.ids_cap = ids_cap
+        cur = torch.cuda.current_stream(dev)
+        mine = torch.cuda.ExternalStream(self._o.stream, device=dev) if self._o.stream else torch.cuda.default_stream(dev)
+        same = cur.cuda_stream == mine.cuda_stream
+        if not same:
+            mine.wait_stream(cur)
+        _chk(lib().rx_plan_download_patterns_device(self._h, C.byref(r)), "rx_plan_download_patterns_device")
+        if not same:
+            cur.wait_stream(mine)
+        ns = self.n_streams
+        res = dict(hits=a["hits"][:ns, :pw], count_total=a["count_total"][:self.nfa.pattern_count], n_patterns=int(r.n_patterns))
+        if ids_cap > 0:
+            res.update(ids=a["ids"][:ids_cap], off=a["off"][:ns], cnt=a["cnt"][:ns], ids_total=a["ids_total"][:1])
+        return res
 
     def run(self, data, want_total=True, register=True, compact_final=0, starts=False):
         """rx_plan_run(): host rows in, host results out in one pipelined call (upload, kernel and download of blocks of
